@@ -21,8 +21,15 @@ tables replicated, one triplet all-gather, every rank evaluating the whole globa
 batch) both lose to one GPU at the same global batch (`--batch N*2048`).
 value = all ranks' interactions / max-over-ranks time.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value,
+ms_per_step, the workload and the per-rank times).  `--full` adds every other measurement
+to the line, each a run of its own after the timed steps: the epoch-inclusive rate, the
+full-sort evaluation throughput, the kernel rooflines, the latency-injection report and
+the CPU baseline (`--no-cpu-baseline` drops the last).  `--dump-outputs DIR` writes what the
+last timed step left (parameters, Adam moments, loss) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -44,6 +51,46 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md chip table (spec)
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_LIMIT_BYTES = 60_000_000  # of files: under 64 MB however a megabyte is counted
+DUMP_WHOLE_BYTES = 1 << 20  # an array up to this size is always written whole
+NPY_HEADER_BYTES = 128
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor) as out_dir/<name>.npy, float32
+    (float64 for a double or integer tensor), DUMP_LIMIT_BYTES of files in all at the most.
+    When the arrays together are larger, those above DUMP_WHOLE_BYTES are cut to their share
+    of what the small ones leave: a sample of the flattened elements at sorted indices drawn
+    from a generator seeded by the array's place in the dict and its size only, so two runs
+    (or two builds) write the same elements.
+    Returns {name: {"shape", "written", "dtype"}} for the log."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: (v if torch.is_tensor(v) else torch.as_tensor(v)).detach() for k, v in arrays.items()}
+    width = {k: 4 if v.dtype in (torch.float32, torch.float16, torch.bfloat16) else 8 for k, v in arrays.items()}
+    size = {k: v.numel() * width[k] for k, v in arrays.items()}
+    budget = DUMP_LIMIT_BYTES - NPY_HEADER_BYTES * len(arrays)
+    cut = set()
+    if sum(size.values()) > budget:
+        cut = {k for k in arrays if size[k] > DUMP_WHOLE_BYTES}
+        budget -= sum(size[k] for k in arrays if k not in cut)
+        if budget <= 0:
+            raise SystemExit(f"--dump-outputs: {len(arrays) - len(cut)} small arrays alone pass the limit")
+    scale = budget / max(sum(size[k] for k in cut), 1)
+    info = {}
+    for place, (name, t) in enumerate(arrays.items()):
+        n = t.numel()
+        flat = t.reshape(-1)
+        if name in cut:
+            idx = np.sort(np.random.default_rng([place, n]).integers(0, n, size=int(n * scale)))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float32 if width[name] == 4 else torch.float64).cpu().numpy()
+        if name not in cut:
+            a = a.reshape(tuple(t.shape))
+        np.save(os.path.join(out_dir, name.replace(os.sep, "_") + ".npy"), a)
+        info[name] = {"shape": list(t.shape), "written": int(a.size), "dtype": str(a.dtype)}
+    return info
 
 
 def spmm_bytes(n_rows, nnz, d):
@@ -358,13 +405,14 @@ def bench_model(args):
 
     it = batches()
     idx = {"i": 0}
+    last = {"loss": None}  # what the last train_step returned (--dump-outputs)
 
     def one_step():
         b = next(it)
         if t.fused:
             model.fused_step(b, t.current_lr())
         else:
-            t.train_step(b, idx["i"], model.calculate_loss)
+            last["loss"] = t.train_step(b, idx["i"], model.calculate_loss)[1]
         idx["i"] += 1
         return b.shape[1]
 
@@ -411,6 +459,45 @@ def bench_model(args):
             ones = torch.ones(1, dtype=torch.float32, device=dev)
             model.comm.allreduce_(ones)
             rccl_world = int(round(float(ones.item())))
+    if args.dump_outputs and rank == 0:
+        # the model's trained tensors as the last timed step left them, and that step's loss
+        arrays = {k: p for k, p in model.named_parameters() if p.requires_grad}
+        eng = getattr(model, "engine", None)
+        # a fused-step model trains its engine's table: p, the Adam moments, the last loss
+        # (loss_out) or, where the engine keeps only that, the running loss sum (loss_acc)
+        for attr in ("p", "m", "v", "loss_out" if hasattr(eng, "loss_out") else "loss_acc"):
+            if torch.is_tensor(getattr(eng, attr, None)):
+                arrays["engine." + attr] = getattr(eng, attr)
+        if last["loss"] is not None:
+            arrays["loss"] = last["loss"]
+        log(f"[bench] --dump-outputs {args.dump_outputs}: {json.dumps(dump_outputs(args.dump_outputs, arrays))}")
+    head = {
+        "metric": METRIC, "value": n / wall, "unit": "interactions/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "warmup_steps_run": n_warm, "ms_per_step": wall * 1e3 / args.steps,
+        "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "full": bool(args.full),
+        "data": f"synthetic Amazon-{w['dataset']}-shaped graph (rsx.synth seed 0)"
+                + ("; N(0,1) features" if w["model"] == "SMORE" else ""),
+        "config": {"workload": w["desc"], "model": w["model"], "embedding_size": int(c["embedding_size"]),
+                   "global_batch": int(getattr(model, "local_batch", args.batch)) * world,
+                   "parallelism": f"{getattr(model, 'scheme', None) or 'usershard'}{world}" if sharded else "single",
+                   "fused_step": bool(t.fused),
+                   "graph_step": t._graph is not None and t._graph.replays > 0},
+        "launcher": os.environ.get("RSX_BENCH_LAUNCHER", "torchrun" if world > 1 else "single process"),
+        "rccl_world_size": rccl_world, "per_rank": per_rank, "model_build_s": build_s,
+    }
+
+    def finish():
+        if rank == 0:
+            _json_line(head)
+        if world > 1 or sim:
+            if getattr(model, "comm", None) is not None:
+                model.comm.close()
+        if world > 1:
+            torch.distributed.destroy_process_group()
+
+    if not args.full:  # the plain run ends here: nothing measured beyond the timed steps
+        return finish()
     model.eval()
     t.evaluate(valid)
     torch.cuda.synchronize()
@@ -460,24 +547,12 @@ def bench_model(args):
         else:
             cpu = cpu_baseline_layergcn(tu_, ti_, nu_, ni, int(c["n_layers"]), float(c["reg_weight"]),
                                         float(c["dropout"]), args.cpu_budget, -(-tu_.size // args.batch))
-    out = {
-        "metric": METRIC, "value": n / wall, "unit": "interactions/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "warmup_steps_run": n_warm, "ms_per_step": wall * 1e3 / args.steps,
-        "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": f"synthetic Amazon-{w['dataset']}-shaped graph (rsx.synth seed 0)"
-                + ("; N(0,1) features" if w["model"] == "SMORE" else ""),
-        "config": {"workload": w["desc"], "model": w["model"], "embedding_size": int(c["embedding_size"]),
-                   "global_batch": int(getattr(model, "local_batch", args.batch)) * world,
-                   "parallelism": f"{getattr(model, 'scheme', None) or 'usershard'}{world}" if sharded else "single",
-                   "fused_step": bool(t.fused),
-                   "graph_step": t._graph is not None and t._graph.replays > 0},
-        "launcher": os.environ.get("RSX_BENCH_LAUNCHER", "torchrun" if world > 1 else "single process"),
-        "rccl_world_size": rccl_world, "per_rank": per_rank,
+    out = head
+    out.update({
         "fullsort_items_per_s": n_eval * ni / eval_s,
         "fullsort": {"eval_users": n_eval, "n_items": ni, "s_per_eval_incl_forward_and_metrics": eval_s},
-        "model_build_s": build_s, "roofline": roof, "roofline_kernels": kernels, "cpu_baseline": cpu,
-    }
+        "roofline": roof, "roofline_kernels": kernels, "cpu_baseline": cpu,
+    })
     if sim:
         Wm = int(sim["world"])
         out["config"]["parallelism"] = f"{model.scheme}{Wm} (latency-injected, rank 0 of {Wm})"
@@ -491,13 +566,7 @@ def bench_model(args):
                    "its 1/W of the users and item rows, a batch of its own; every collective a comm-stream "
                    "stand-in of the modelled time") +
                   "): the job's rate is world x value; the fullsort figures are this rank's users only"))
-    if rank == 0:
-        _json_line(out)
-    if world > 1 or sim:
-        if getattr(model, "comm", None) is not None:
-            model.comm.close()
-    if world > 1:
-        torch.distributed.destroy_process_group()
+    finish()
 
 
 def bench_c1_cpu(args):
@@ -553,8 +622,11 @@ def bench_c1_cpu(args):
     t0 = time.perf_counter()
     n = sum(epoch(1 + e) for e in range(n_ep))
     wall = time.perf_counter() - t0
+    if args.dump_outputs:
+        arrays = {k: p for k, p in model.named_parameters() if p.requires_grad}
+        log(f"[bench] --dump-outputs {args.dump_outputs}: {json.dumps(dump_outputs(args.dump_outputs, arrays))}")
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         tr_df = df[df.x_label == 0]
         tu_, ti_ = tr_df.userID.values.astype(np.int64), tr_df.itemID.values.astype(np.int64)
         cpu = cpu_baseline_layergcn(tu_, ti_, int(df.userID.max()) + 1, int(df.itemID.max()) + 1, 2, 1e-2, 0.1,
@@ -858,7 +930,15 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="default 200 (c4: 20)")
     ap.add_argument("--warmup", type=int, default=None, help="default 20 (c4: 3)")
     ap.add_argument("--batch", type=int, default=2048)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and report everything beyond the headline figure: the "
+                         "epoch-inclusive rate, the full-sort evaluation, the kernel rooflines, the "
+                         "latency-injection report (RSX_COMM_SIM) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them left (parameters, Adam moments, loss) "
+                         "as DIR/<name>.npy, float32/float64, 64 MB in all at the most (a fixed seeded sample of "
+                         "larger tables); rank 0 writes; nothing is written with --dry-run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--sharded", action="store_true",
                     help="use the row-sharded engine even at N=1 (measures its host/launch overhead)")
     ap.add_argument("--dist", choices=["dp", "rowshard"], default=None,
@@ -1081,6 +1161,49 @@ def main():
     else:
         total_inter = float(done["inter"])
     loss_mean = float(eng.loss_acc.item()) / max(eng.step_count, 1)
+    if args.dump_outputs:
+        # the engine's state as the last timed step left it: the [users; items] table, the Adam
+        # moments where this engine keeps them whole, and that step's loss
+        if hasattr(eng, "flush"):  # row-sharded: completes a deferred all-gather (every rank calls it)
+            eng.flush()
+        if rank == 0:
+            arrays = {"params": eng.p, "loss": eng.loss_out}
+            for name, attr in (("adam_m", "m"), ("adam_v", "v")):
+                if torch.is_tensor(getattr(eng, attr, None)):
+                    arrays[name] = getattr(eng, attr)
+            log(f"[bench] --dump-outputs {args.dump_outputs}: "
+                f"{json.dumps(dump_outputs(args.dump_outputs, arrays))}")
+    head = {
+        "metric": METRIC,
+        "value": total_inter / wall,
+        "unit": "interactions/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": wall * 1e3 / args.steps,
+        "higher_is_better": True,
+        # c4: the graph is fixed whatever N (strong), each rank's batch is its own users' 2048
+        "scaling": "strong" if big else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "full": bool(args.full),
+    }
+    if not args.full:  # the plain run ends here: nothing measured beyond the timed steps
+        if rank == 0:
+            _json_line(dict(head, config={"workload": desc, "model": "LightGCN", "n_layers": args.n_layers,
+                                          "embedding_size": d, "global_batch": B * world, "per_rank_batch": B,
+                                          "parallelism": (f"dp{world}" if dp else
+                                                          f"rowshard{world}" if sharded else "single")},
+                            launcher=os.environ.get("RSX_BENCH_LAUNCHER",
+                                                    "torchrun" if world > 1 else "single process"),
+                            rccl_world_size=rccl_world, dp_replicas_bit_identical=replicas_identical,
+                            per_rank=per_rank, gpu_ms_per_step_events=gpu_ms / args.steps,
+                            train_loss_mean=loss_mean))
+        if hasattr(eng, "close"):
+            eng.close()
+        if sharded or dp:
+            torch.distributed.destroy_process_group()
+        return
 
     # epoch-inclusive rate: one whole fresh epoch, its sampling launch included
     epoch_rate = None
@@ -1266,18 +1389,7 @@ def main():
     if rank == 0:
         ms = wall * 1e3 / args.steps
         out = {
-            "metric": METRIC,
-            "value": total_inter / wall,
-            "unit": "interactions/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms,
-            "higher_is_better": True,
-            # c4: the graph is fixed whatever N (strong), each rank's batch is its own users' 2048
-            "scaling": "strong" if big else "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
+            **head,
             "data": (f"synthetic Amazon-{'sports' if args.workload == 'c2' else 'baby'}-shaped graph (rsx.synth, "
                      "seed=rank; Zipf(0.8) items, 5-core users, reference split rule); xavier-uniform init, seed 999")
                     if not big else

@@ -70,6 +70,43 @@ def test_explicit_master_port_wins():
     assert json.loads(p.stdout.decode().strip())["master_port"] == 23457
 
 
+def test_dump_outputs_whole_then_a_fixed_sample_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: arrays within the limit are written whole (float32, doubles and integers
+    as float64); beyond it the large ones are cut to their share, the same elements on every call."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    g = torch.Generator().manual_seed(3)
+    arrays = {"params": torch.randn(300, 7, generator=g), "loss": torch.randn(1, generator=g).double(),
+              "count": torch.arange(5)}
+    info = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    p = np.load(tmp_path / "a" / "params.npy")
+    assert p.dtype == np.float32 and np.array_equal(p, arrays["params"].numpy())
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "a" / "count.npy"), np.arange(5, dtype=np.float64))
+    assert info["params"] == {"shape": [300, 7], "written": 2100, "dtype": "float32"}
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    monkeypatch.setattr(bench, "DUMP_WHOLE_BYTES", 64)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 4096
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in arrays}
+    assert b["loss"].shape == (1,) and b["count"].shape == (5,)  # the small ones stay whole
+    assert 500 < b["params"].size < 2100 and b["params"].ndim == 1
+    assert np.isin(b["params"], arrays["params"].numpy()).all()
+    for n in arrays:
+        assert np.array_equal(b[n], np.load(tmp_path / "c" / (n + ".npy")))
+
+
+def test_full_and_dump_outputs_are_options_of_the_dry_run_too(tmp_path):
+    p = _run(["--gpus", "1", "--dry-run", "--full", "--dump-outputs", str(tmp_path / "o")])
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    assert json.loads(p.stdout.decode().strip())["dry_run"] is True
+
+
 def test_replica_hash_sees_permutations_and_cancelling_differences():
     import torch
 

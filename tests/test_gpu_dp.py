@@ -22,6 +22,7 @@ from test_dist_gloo import D, LR, NI, NU, REG, _local_graph
 
 pytestmark = pytest.mark.gpu
 
+HOT_RUNS = 8  # single-GPU reference runs of a hot case (test_dp_one_rank_rccl_equals_single_gpu_step)
 
 
 def _trip(s, r, hot=False):
@@ -116,7 +117,11 @@ def _rccl_worker(rank, world, store, out_dir, k, graph="1", hot=False):
     U0, I0 = z["init.embedding_dict.user_emb"], z["init.embedding_dict.item_emb"]
     dp = DataParallelLightGCNEngine(z["train_u"], z["train_i"], nu, ni, 64, k, 1e-2, 1e-3, "cuda:0", U0, I0,
                                     batch=512)
-    one = LightGCNEngine(z["train_u"], z["train_i"], nu, ni, 64, k, 1e-2, 1e-3, "cuda:0", U0, I0, batch=512)
+    # hot: HOT_RUNS single-GPU engines on the same triplets (its float atomics order differently
+    # from run to run, see the test); `one` is the first
+    ones = [LightGCNEngine(z["train_u"], z["train_i"], nu, ni, 64, k, 1e-2, 1e-3, "cuda:0", U0, I0, batch=512)
+            for _ in range(HOT_RUNS if hot else 1)]
+    one = ones[0]
     trips = torch.from_numpy(z["epoch0_triplets"].astype(np.int64)).cuda()
     if hot:  # one positive item for every triplet, one user for half of them: runs of equal
         trips = trips.clone()  # rows crossing many chunks of the solo step's run places
@@ -126,12 +131,13 @@ def _rccl_worker(rank, world, store, out_dir, k, graph="1", hot=False):
     for s in range(6):  # eager, eager (warm), captured, replayed ...; a partial batch at the end
         t = trips[:, s * 512:(s + 1) * 512] if s < 5 else trips[:, 5 * 512: 5 * 512 + 300]
         dp.step(t)
-        one.step(triplets=t)
+        for o in ones:
+            o.step(triplets=t)
         la.append(float(dp.loss_out.item()))
         lb.append(float(one.loss_out.item()))
     torch.cuda.synchronize()
     np.savez(os.path.join(out_dir, "rccl.npz"), la=np.array(la), lb=np.array(lb), pa=dp.p.cpu().numpy(),
-             pb=one.p.cpu().numpy(), ma=dp.m.cpu().numpy(), mb=one.m.cpu().numpy(),
+             pb=np.stack([o.p.cpu().numpy() for o in ones]), ma=dp.m.cpu().numpy(), mb=one.m.cpu().numpy(),
              graphs=np.array(sorted(dp._graphs)))
     dp.close()
     dist.destroy_process_group()
@@ -144,12 +150,25 @@ def test_dp_one_rank_rccl_equals_single_gpu_step(k, graph, hot):
     the same arithmetic as the single-GPU stored-layer step (only the BPR scatter's float
     atomics order differently run to run).  hot: the eager one-rank step is the solo path
     (the loss pass takes the run places, csrc/dp.hip) and meets runs of equal rows that
-    cross chunk boundaries."""
+    cross chunk boundaries.
+
+    The tables after the six steps agree within 1e-6 at every element.  On the hot triplets
+    the single-GPU step is not one value there: a hot row's gradient is ~1,000 float atomics,
+    and six Adam steps turn their order into a spread of the parameter of up to 1.2e-6
+    between two runs of the single-GPU engine itself (measured over 24 runs: one element of
+    one row, 0.17e-6 .. 1.39e-6 from the DP step's value, which is bit-identical in every
+    run; beyond 1e-6 in 5 of the 24).  So the hot cases run the single-GPU engine HOT_RUNS
+    times and ask, element by element, that the DP step's value lies within 1e-6 of one of
+    them: a single run missing at 5/24 leaves (5/24)^8 = 4e-6 for all eight.  The cold cases
+    (run-to-run spread measured at 7e-8) keep the one run."""
     with tempfile.TemporaryDirectory() as d:
         mp.spawn(_rccl_worker, args=(1, store_path(), d, k, graph, hot), nprocs=1, join=True)
         z = dict(np.load(os.path.join(d, "rccl.npz")))
     np.testing.assert_allclose(z["la"], z["lb"], rtol=1e-6)
-    np.testing.assert_allclose(z["pa"], z["pb"], rtol=0, atol=1e-6)
+    assert z["pb"].shape[0] == (HOT_RUNS if hot else 1)
+    nearest = np.abs(z["pb"].astype(np.float64) - z["pa"].astype(np.float64)).min(axis=0)
+    worst = np.unravel_index(np.argmax(nearest), nearest.shape)
+    assert nearest[worst] <= 1e-6, (worst, nearest[worst], z["pa"][worst], z["pb"][(slice(None),) + worst])
     # hot rows sum ~1,000 float atomics in the single-GPU step: its moments carry their order
     np.testing.assert_allclose(z["ma"], z["mb"], rtol=0, atol=1e-6 if hot else 1e-7)
     if graph == "1":

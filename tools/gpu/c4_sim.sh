@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 OUT=${OUT:-gpurun_out/c4sim}
 mkdir -p $OUT
-A="--workload c4 --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --eval-users 4096"
+A="--full --workload c4 --steps ${STEPS:-8} --warmup 2 --no-cpu-baseline --eval-users 4096"
 for W in ${WS:-8 4 2}; do
   C=$((8 / W))
   RSX_COMM_SIM=$W timeout -k 10 500 python bench.py $A > $OUT/sim_w$W.json 2> $OUT/sim_w$W.err || { tail -20 $OUT/sim_w$W.err; exit 1; }
