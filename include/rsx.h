@@ -1197,6 +1197,103 @@ int rsx_cpu_gcn_step(int32_t kind, const int64_t* rowptr, const int32_t* col, co
                      float* p, float* m, float* v, int64_t step, float lr, float beta1, float beta2, float eps,
                      float weight_decay, float* ws, size_t ws_floats, float* loss_out);
 
+/* ------------------------------------------------------------------------ */
+/* BPR / VBPR matrix factorisation (mf.hip)                                   */
+/* ------------------------------------------------------------------------ */
+/*
+ * A Linear applied to selected rows of a fixed table (VBPR's item_linear on the raw
+ * item features, reference src/models/vbpr.py:70, which projects every item on every
+ * step; only the batch's items reach the loss, :90-93):
+ *   out[r, 0:out_dim] = x[rows[r], :] W^T + b      r < n
+ * x [n_src, in_dim] f32, W [out_dim, in_dim] (nn.Linear layout), b [out_dim] or NULL,
+ * rows int64 [n] (any order, duplicates allowed; every entry in [0, n_src)) or NULL =
+ * rows 0..n-1; out has row stride ld_out >= out_dim, a multiple of 4, and is 16-byte
+ * aligned (float4 stores; else RSX_ERR_ARG); only out_dim columns of a row are written, so
+ * the result can fill the right half of a wider table.  f32 MFMA; the
+ * gathered rows are read in place through `rows`.  in_dim a multiple of 4 (a ragged
+ * last 32-column step is masked), out_dim in {32, 64, 128}, else RSX_ERR_UNSUPPORTED.
+ */
+int rsx_linear_rows_fwd(const float* x, const float* W, const float* b, const int64_t* rows, int64_t n,
+                        int32_t in_dim, int32_t out_dim, float* out, int64_t ld_out, rsx_stream_t stream);
+/*
+ * The matching weight and bias gradients (AddmmBackward of the same site) through the
+ * same row indices: dw[out_dim, in_dim] = sum_r g[r, :]^T x[rows[r], :], and, when db is
+ * non-NULL, db[out_dim] = sum_r g[r, :];  g is 16-byte aligned with row stride ld_g >=
+ * out_dim, a multiple of 4 (float4 loads; else RSX_ERR_ARG).
+ * rsx_linear_wgrad's split reduction with the row index in its loads: deterministic, and
+ * with rows = NULL and ld_g = out_dim dw has rsx_linear_wgrad's bits.  Same shapes as
+ * rsx_linear_rows_fwd.  Workspace: rsx_linear_rows_wgrad_ws_bytes, which does not decrease
+ * with n: a workspace sized for n rows serves every call with fewer.
+ */
+size_t rsx_linear_rows_wgrad_ws_bytes(int64_t n, int32_t out_dim, int32_t in_dim);
+int rsx_linear_rows_wgrad(const float* g, int64_t ld_g, const float* x, const int64_t* rows, int64_t n,
+                          int32_t out_dim, int32_t in_dim, float* dw, float* db, void* ws, size_t ws_bytes,
+                          rsx_stream_t stream);
+
+/*
+ * One BPR or VBPR training batch (reference src/models/bpr.py:67-87, vbpr.py:69-98,
+ * src/common/loss.py:33-51, the autograd backward and torch.optim.Adam,
+ * src/common/trainer.py:133,238) in one host call.
+ *   F == 0 (BPR):  user row U[u] (du = d), item row e(i) = I[i];
+ *   F > 0 (VBPR):  user row U[u] (du = 2 d), item row e(i) = [ I[i] , X[i] W^T + b ]
+ *                  (column order of vbpr.py:71), X [n_items, F] fixed raw features.
+ *   loss = -mean log(1e-10 + sigmoid(<U[u], e(p)> - <U[u], e(n)>))
+ *          + reg (|U_b|_F + |P_b|_F + |N_b|_F) / batch
+ * over the batch's rows (duplicates are separate rows): RSX_BPR_LIGHTGCN's formula.
+ * Launches: (sampler), projection of the batch's 2 batch item rows (rsx_linear_rows_fwd,
+ * rows = triplets + batch), loss forward (f64 partials of the loss and the three squared
+ * norms), loss backward (every block re-reduces the partials in one order; row gradients
+ * scattered with f32 atomics into gU / gI, the projected rows' gradients stored),
+ * rsx_linear_rows_wgrad, then ONE dense Adam launch over U, I, W, b: rows outside the
+ * batch have zero gradient, their moments still decay and they still move, as
+ * torch.optim.Adam on the reference's dense gradients.  That launch also clears the
+ * entries of gU / gI it read as non-zero, so the scratch is zero again for the next step.
+ * Buffers (f32): U, mU, vU [n_users, du]; I, mI, vI [n_items, d]; W, mW, vW [d, F]; b, mb,
+ * vb [d] (W.. vb and X: F > 0 only); gU [n_users, du], gI [n_items, d]: zero before the
+ * first step; gW [d, F], gb [d]: written.  triplets int64 [3][batch]; with `sample` they
+ * are drawn first (rsx_sample_triplets' contract, as rsx_lgcn_step).  loss_out / loss_acc /
+ * halt / tag as in rsx_lgcn_step: the first NaN loss sets halt = {1, tag} and from then on
+ * the parameters and moments stay untouched.  ws >= rsx_mf_ws_bytes(batch, d, F), which does
+ * not decrease with batch: sized once for the configured batch it serves every shorter one
+ * (the last batch of an epoch).
+ * d in {32, 64, 128}, F a multiple of 4, else RSX_ERR_UNSUPPORTED.
+ */
+typedef struct rsx_mf_step_args {
+    int64_t n_users, n_items;
+    int32_t d, F;
+    float reg;
+    int32_t pad0;
+    float* U; float* mU; float* vU;
+    float* I; float* mI; float* vI;
+    float* W; float* mW; float* vW;
+    float* b; float* mb; float* vb;
+    const float* X;
+    float* gU; float* gI; float* gW; float* gb;
+    int64_t* triplets;  /* [3][batch] */
+    int64_t batch;
+    const rsx_sampler_args* sample;
+    rsx_adam adam;
+    float* loss_out;    /* [1] */
+    double* loss_acc;   /* [1] or NULL */
+    void* ws; size_t ws_bytes;
+    int32_t* halt;      /* [2] or NULL */
+    int64_t tag;
+    /* optional device step counter (int64 [1]): the loss launch adds 1 to it and the Adam
+     * launch reads it instead of adam.step, so a captured step advances on every replay */
+    int64_t* step_dev;
+} rsx_mf_step_args;
+
+size_t rsx_mf_ws_bytes(int64_t batch, int32_t d, int32_t F);
+int rsx_mf_step(const rsx_mf_step_args* st, rsx_stream_t stream);
+/*
+ * The same loss and its raw gradients without the optimiser (the autograd path): reads
+ * U, I, W, b, X, triplets, batch, reg, ws of `st` (moments, adam, sample, halt, the g*
+ * and step_dev fields are ignored) and writes loss_out (and adds into loss_acc when non-NULL) and the
+ * dense gradients gU [n_users, du], gI [n_items, d] (zero-filled here, then scattered),
+ * gW [d, F], gb [d] (F > 0).
+ */
+int rsx_mf_loss_grad(const rsx_mf_step_args* st, float* gU, float* gI, float* gW, float* gb, rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

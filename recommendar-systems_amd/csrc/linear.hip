@@ -88,11 +88,16 @@ static WgPlan wg_plan(int64_t n, int out_dim, int in_dim, int max_ig = 4, int64_
 // 16x16x4 f32 MFMA tiles from the g chunk already in LDS) and, in the blocks of
 // the first i column, the bias-gradient partials colsum(g) (the av values the dW
 // MFMAs read, summed per lane) into the slot's tail [out] floats.
-template <int IG, int OTB, bool DX>
+//
+// GATHER (rsx_linear_rows_wgrad, the VBPR projection's weight gradient over the batch's item
+// rows): logical row r is x row xrows[r] (NULL: r) and g has row stride ld_g; nothing else
+// changes, so xrows = NULL, ld_g = out_dim gives the plain kernel's bits.
+template <int IG, int OTB, bool DX, bool GATHER = false>
 __device__ __forceinline__ void wgrad_partial_body(int64_t bid, const float* __restrict__ g, const float* __restrict__ x,
                                                    int64_t n, int out_dim, int in_dim, int64_t rows, int64_t nob,
                                                    int64_t nib, float* __restrict__ part, const float* __restrict__ W,
-                                                   float* __restrict__ dx, int do_db);
+                                                   float* __restrict__ dx, int do_db,
+                                                   const int64_t* __restrict__ xrows = nullptr, int64_t ld_g = 0);
 
 template <int IG, int OTB, bool DX = false>
 __global__ __launch_bounds__(256) void wgrad_partial(const float* __restrict__ g, const float* __restrict__ x,
@@ -101,6 +106,16 @@ __global__ __launch_bounds__(256) void wgrad_partial(const float* __restrict__ g
                                                      const float* __restrict__ W = nullptr, float* __restrict__ dx = nullptr,
                                                      int do_db = 0) {
     wgrad_partial_body<IG, OTB, DX>(blockIdx.x, g, x, n, out_dim, in_dim, rows, nob, nib, part, W, dx, do_db);
+}
+
+template <int IG, int OTB>
+__global__ __launch_bounds__(256) void wgrad_partial_rows(const float* __restrict__ g, int64_t ld_g,
+                                                          const float* __restrict__ x,
+                                                          const int64_t* __restrict__ xrows, int64_t n, int out_dim,
+                                                          int in_dim, int64_t rows, int64_t nob, int64_t nib,
+                                                          float* __restrict__ part) {
+    wgrad_partial_body<IG, OTB, false, true>(blockIdx.x, g, x, n, out_dim, in_dim, rows, nob, nib, part, nullptr,
+                                             nullptr, 0, xrows, ld_g);
 }
 
 // Two fused projection backwards of the same rows and output width in one launch (SMORE's
@@ -125,11 +140,12 @@ __global__ __launch_bounds__(256) void wgrad_partial_pair(LbwdProb p0, LbwdProb 
                                       q.in_dim, q.rows, 1, q.nib, q.part, q.W, q.dx, q.do_db);
 }
 
-template <int IG, int OTB, bool DX>
+template <int IG, int OTB, bool DX, bool GATHER>
 __device__ __forceinline__ void wgrad_partial_body(int64_t bid, const float* __restrict__ g, const float* __restrict__ x,
                                                    int64_t n, int out_dim, int in_dim, int64_t rows, int64_t nob,
                                                    int64_t nib, float* __restrict__ part, const float* __restrict__ W,
-                                                   float* __restrict__ dx, int do_db) {
+                                                   float* __restrict__ dx, int do_db,
+                                                   const int64_t* __restrict__ xrows, int64_t ld_g) {
     constexpr int RW = 4 / OTB;
     constexpr int OC = 32 * OTB, IC = 32 * IG;   // block's o / i columns
     constexpr int CH = kWgChunk * RW;            // rows per block step
@@ -164,12 +180,15 @@ __device__ __forceinline__ void wgrad_partial_body(int64_t bid, const float* __r
             if (e < NG) {
                 const int rr = e / (OC / 4), cc = (e % (OC / 4)) * 4;
                 const int64_t row = c0 + rr;
-                if (row < r1) t = ld4(g + row * out_dim + ob + cc);
+                if (row < r1) t = ld4(g + row * (GATHER ? ld_g : (int64_t)out_dim) + ob + cc);
             } else if (e < NG + NX) {
                 const int e2 = e - NG;
                 const int rr = e2 / (IC / 4), cc = (e2 % (IC / 4)) * 4;
                 const int64_t row = c0 + rr;
-                if (row < r1 && ib + cc < in_dim) t = ld4(x + row * in_dim + ib + cc);
+                if (row < r1 && ib + cc < in_dim) {
+                    const int64_t xr = (GATHER && xrows) ? xrows[row] : row;
+                    t = ld4(x + xr * in_dim + ib + cc);
+                }
             }
             v[k] = t;
         }
@@ -429,6 +448,26 @@ __global__ __launch_bounds__(256) void wgrad_reduce_dwdb_pair(DwdbProb p0, DwdbP
     }
 }
 
+// Column sums of g [n, out_dim] (row stride ld_g) over a block's contiguous share of the rows:
+// thread (rg, col) adds rows rg, rg + RG, ... of the share in order, the RG row groups are
+// added in order, and wgrad_reduce adds the blocks' slots in order (deterministic).
+__global__ __launch_bounds__(256) void colsum_partial(const float* __restrict__ g, int64_t ld_g, int64_t n,
+                                                      int out_dim, int64_t rows, float* __restrict__ part) {
+    __shared__ float red[256];
+    const int col = threadIdx.x % out_dim, rg = threadIdx.x / out_dim, RG = 256 / out_dim;
+    const int64_t r0 = (int64_t)blockIdx.x * rows, r1 = min(n, r0 + rows);
+    float acc = 0.f;
+    for (int64_t r = r0 + rg; r < r1; r += RG) acc += g[r * ld_g + col];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    if (rg == 0) {
+        for (int k = 1; k < RG; ++k) acc += red[k * out_dim + col];
+        part[(int64_t)blockIdx.x * out_dim + col] = acc;
+    }
+}
+
+constexpr int kColsumBlocks = 64;
+
 }  // namespace rsx
 
 using namespace rsx;
@@ -606,5 +645,81 @@ extern "C" int rsx_linear_wgrad(const float* g, const float* x, int64_t n, int32
 #undef RSX_WG
     hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)((sz + 63) / 64)), dim3(256), 0, s, (const float*)part, p.slots(),
                        sz, dw);
+    return last_rc();
+}
+
+// An upper bound of wg_plan(m, ...).slots() for every m <= n: the plan's split count before
+// its "at least one chunk per row group" cap (which makes the exact count non-monotonic in
+// n: fewer rows can round to more splits).  splits = ceil(n / rows) with rows >= n / s, so
+// splits <= s, and s's other two caps (the wave budget, the partial bytes) grow with n.
+static int64_t wg_slots_bound(int64_t n, int out_dim, int in_dim) {
+    const int it = (in_dim + 31) / 32, ot = out_dim / 32;
+    const int ig = (it % 4 == 0) ? 4 : (it % 2 == 0) ? 2 : 1;
+    const int otb = ot % 4 == 0 ? 4 : ot % 2 == 0 ? 2 : 1;
+    const int rw = 4 / otb;
+    const int64_t grid_waves = (int64_t)(ot / otb) * (it / ig) * 4;
+    int64_t s = kWgTargetWaves / grid_waves;
+    const int64_t in_bytes = n * (int64_t)(out_dim + in_dim) * 4;
+    const int64_t slot_bytes = (int64_t)out_dim * in_dim * 4;
+    const int64_t cap_bytes = in_bytes / 4 > (4 << 20) ? in_bytes / 4 : (4 << 20);
+    s = std::min(s, cap_bytes / (slot_bytes * rw));
+    return std::max<int64_t>(s, 1) * rw;
+}
+
+// Monotonic in n: a workspace sized for n rows serves every call with fewer rows (a shorter
+// last batch of an epoch).
+extern "C" size_t rsx_linear_rows_wgrad_ws_bytes(int64_t n, int32_t out_dim, int32_t in_dim) {
+    if (n <= 0 || (out_dim != 32 && out_dim != 64 && out_dim != 128) || in_dim <= 0 || (in_dim % 4)) return 0;
+    return (size_t)wg_slots_bound(n, out_dim, in_dim) * (size_t)out_dim * (size_t)in_dim * sizeof(float) +
+           (size_t)kColsumBlocks * out_dim * sizeof(float);
+}
+
+// dw = sum_r g[r]^T x[xrows[r]], db = sum_r g[r] (reference src/models/vbpr.py:70's AddmmBackward on
+// the batch's item rows): rsx_linear_wgrad's plan and kernels with the row index in the x loads.
+extern "C" int rsx_linear_rows_wgrad(const float* g, int64_t ld_g, const float* x, const int64_t* xrows, int64_t n,
+                                     int32_t out_dim, int32_t in_dim, float* dw, float* db, void* ws, size_t ws_bytes,
+                                     rsx_stream_t stream) {
+    if (n < 0 || out_dim <= 0 || in_dim <= 0 || !dw) return RSX_ERR_ARG;
+    if ((out_dim != 32 && out_dim != 64 && out_dim != 128) || (in_dim % 4)) return RSX_ERR_UNSUPPORTED;
+    if (n > 0 && (!g || !x || ld_g < out_dim || (ld_g % 4) || (reinterpret_cast<uintptr_t>(g) & 15))) return RSX_ERR_ARG;
+    hipStream_t s = as_stream(stream);
+    const int64_t sz = (int64_t)out_dim * in_dim;
+    if (n == 0) {
+        hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)((sz + 63) / 64)), dim3(256), 0, s, (const float*)nullptr, 0,
+                           sz, dw);
+        if (db) hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)((out_dim + 63) / 64)), dim3(256), 0, s,
+                                   (const float*)nullptr, 0, (int64_t)out_dim, db);
+        return last_rc();
+    }
+    if (ws_bytes < rsx_linear_rows_wgrad_ws_bytes(n, out_dim, in_dim) || !ws) return RSX_ERR_WORKSPACE;
+    const WgPlan p = wg_plan(n, out_dim, in_dim);
+    float* part = static_cast<float*>(ws);
+    const dim3 grid((unsigned)(p.nob * p.nib * p.splits));
+#define RSX_WGR(IG, OTB)                                                                                          \
+    hipLaunchKernelGGL((wgrad_partial_rows<IG, OTB>), grid, dim3(256), 0, s, g, ld_g, x, xrows, n, (int)out_dim,  \
+                       (int)in_dim, p.rows, p.nob, p.nib, part)
+    switch (p.ig * 8 + p.otb) {
+        case 4 * 8 + 4: RSX_WGR(4, 4); break;
+        case 4 * 8 + 2: RSX_WGR(4, 2); break;
+        case 4 * 8 + 1: RSX_WGR(4, 1); break;
+        case 2 * 8 + 4: RSX_WGR(2, 4); break;
+        case 2 * 8 + 2: RSX_WGR(2, 2); break;
+        case 2 * 8 + 1: RSX_WGR(2, 1); break;
+        case 1 * 8 + 4: RSX_WGR(1, 4); break;
+        case 1 * 8 + 2: RSX_WGR(1, 2); break;
+        default: RSX_WGR(1, 1); break;
+    }
+#undef RSX_WGR
+    hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)((sz + 63) / 64)), dim3(256), 0, s, (const float*)part, p.slots(),
+                       sz, dw);
+    if (db) {
+        float* cpart = reinterpret_cast<float*>(static_cast<char*>(ws) + rsx_linear_wgrad_ws_bytes(n, out_dim, in_dim));
+        const int nb = (int)std::min<int64_t>(kColsumBlocks, (n + 63) / 64);
+        const int64_t rows = (n + nb - 1) / nb;
+        const int nbu = (int)((n + rows - 1) / rows);  // blocks with at least one row
+        hipLaunchKernelGGL(colsum_partial, dim3(nbu), dim3(256), 0, s, g, ld_g, n, (int)out_dim, rows, cpart);
+        hipLaunchKernelGGL(wgrad_reduce, dim3((unsigned)((out_dim + 63) / 64)), dim3(256), 0, s, (const float*)cpart,
+                           nbu, (int64_t)out_dim, db);
+    }
     return last_rc();
 }

@@ -107,6 +107,15 @@ class DpStep(C.Structure):
                 ("halt", P), ("cap", I64), ("slots", P), ("work", P), ("work_bytes", C.c_size_t)]
 
 
+class MfStep(C.Structure):
+    _fields_ = [("n_users", I64), ("n_items", I64), ("d", I32), ("F", I32), ("reg", F32), ("pad0", I32),
+                ("U", P), ("mU", P), ("vU", P), ("I", P), ("mI", P), ("vI", P), ("W", P), ("mW", P), ("vW", P),
+                ("b", P), ("mb", P), ("vb", P), ("X", P), ("gU", P), ("gI", P), ("gW", P), ("gb", P),
+                ("triplets", P), ("batch", I64), ("sample", C.POINTER(SamplerArgs)), ("adam", Adam),
+                ("loss_out", P), ("loss_acc", P), ("ws", P), ("ws_bytes", C.c_size_t), ("halt", P), ("tag", I64),
+                ("step_dev", P)]
+
+
 RSX_COLL_ALLREDUCE, RSX_COLL_ALLGATHER, RSX_COLL_REDUCESCATTER = 0, 1, 2
 RSX_COLL_F32, RSX_COLL_I64 = 0, 1
 HOST_COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, I32, P, I64, I32, P)
@@ -211,6 +220,12 @@ def _declare(lib):
         "rsx_edge_dropout_ws_bytes": (C.c_size_t, [I64, I64, I64]),
         "rsx_edge_dropout_build": (C.c_int, [P, P, P, I64, I64, I64, P, P, P, P, P, P, P, C.c_size_t, P]),
         "rsx_smore_unit_weights_bwd": (C.c_int, [P, I64, P, P, P, I32, I32, P, P, P, P]),
+        "rsx_linear_rows_fwd": (C.c_int, [P, P, P, P, I64, I32, I32, P, I64, P]),
+        "rsx_linear_rows_wgrad_ws_bytes": (C.c_size_t, [I64, I32, I32]),
+        "rsx_linear_rows_wgrad": (C.c_int, [P, I64, P, P, I64, I32, I32, P, P, P, C.c_size_t, P]),
+        "rsx_mf_ws_bytes": (C.c_size_t, [I64, I32, I32]),
+        "rsx_mf_step": (C.c_int, [C.POINTER(MfStep), P]),
+        "rsx_mf_loss_grad": (C.c_int, [C.POINTER(MfStep), P, P, P, P, P]),
         "rsx_cpu_spmm": (C.c_int, [P, P, P, I64, P, I32, P]),
         "rsx_cpu_propagate_mean": (C.c_int, [P, P, P, I64, P, I32, I32, P]),
         "rsx_cpu_layergcn_forward": (C.c_int, [P, P, P, I64, P, I32, I32, P, P, P]),
@@ -246,6 +261,8 @@ EXPORTED = ["rsx_version", "rsx_csr_schedule_host", "rsx_csr_schedule_rebind", "
             "rsx_smore_unit_weights", "rsx_smore_unit_weights_bwd", "rsx_mg_alpha_ws_bytes", "rsx_mg_alpha",
             "rsx_axpy_multi", "rsx_knn_ws_bytes", "rsx_knn_graph", "rsx_adj_build_ws_bytes", "rsx_adj_build",
             "rsx_edge_dropout_ws_bytes", "rsx_edge_dropout_build", "rsx_nan_gate",
+            "rsx_linear_rows_fwd", "rsx_linear_rows_wgrad_ws_bytes", "rsx_linear_rows_wgrad", "rsx_mf_ws_bytes",
+            "rsx_mf_step", "rsx_mf_loss_grad",
             "rsx_cpu_spmm", "rsx_cpu_propagate_mean", "rsx_cpu_layergcn_forward", "rsx_cpu_layergcn_backward",
             "rsx_cpu_bpr", "rsx_cpu_fullsort_topk", "rsx_cpu_adam", "rsx_cpu_gcn_step_ws_floats", "rsx_cpu_gcn_step"]
 

@@ -449,6 +449,43 @@ def linear_wgrad(g: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     return dw
 
 
+def linear_rows_fwd(x: torch.Tensor, W: torch.Tensor, b: torch.Tensor | None, rows: torch.Tensor | None,
+                    out: torch.Tensor | None = None, col0: int = 0) -> torch.Tensor:
+    """out[r, col0 : col0 + out_dim] = x[rows[r]] W^T + b (rsx_linear_rows_fwd; VBPR's
+    item_linear on the batch's item rows, reference vbpr.py:70).  rows None: every row of x.
+    `out` [n, >= col0 + out_dim] is written in those columns only (a fresh [n, out_dim]
+    tensor when None)."""
+    _gpu(x, W, b, rows)
+    n = x.shape[0] if rows is None else rows.numel()
+    o, i = W.shape
+    if out is None:
+        out = torch.empty(n, o, dtype=torch.float32, device=x.device)
+    _gpu(out)
+    if out.shape[0] != n or out.shape[1] < col0 + o:
+        raise ValueError("linear_rows_fwd: out is too small")
+    dst = C.c_void_p(out.data_ptr() + 4 * col0)
+    L.check(L.lib().rsx_linear_rows_fwd(_p(x), _p(W), _p(b), _p(rows), n, i, o, dst, out.shape[1], _stream()),
+            "rsx_linear_rows_fwd")
+    return out
+
+
+def linear_rows_wgrad(g: torch.Tensor, x: torch.Tensor, rows: torch.Tensor | None, out_dim: int | None = None,
+                      bias: bool = True):
+    """(dW, db) = (sum_r g[r]^T x[rows[r]], sum_r g[r]) (rsx_linear_rows_wgrad); g [n, ld_g]
+    of which the first out_dim columns are the gradient rows (out_dim None: all of them)."""
+    _gpu(g, x, rows)
+    n, ld_g = g.shape
+    o = ld_g if out_dim is None else int(out_dim)
+    i = x.shape[1]
+    dw = torch.empty(o, i, dtype=torch.float32, device=g.device)
+    db = torch.empty(o, dtype=torch.float32, device=g.device) if bias else None
+    lib = L.lib()
+    ws = _ws(g.device, lib.rsx_linear_rows_wgrad_ws_bytes(n, o, i))
+    L.check(lib.rsx_linear_rows_wgrad(_p(g), ld_g, _p(x), _p(rows), n, o, i, _p(dw), _p(db), _p(ws), ws.numel(),
+                                      _stream()), "rsx_linear_rows_wgrad")
+    return dw, db
+
+
 def score_dense(user_emb: torch.Tensor, users: torch.Tensor | None, item_emb: torch.Tensor) -> torch.Tensor:
     """scores = user_emb[users] @ item_emb.T (reference lightgcn.py:164)."""
     _gpu(user_emb, users, item_emb)

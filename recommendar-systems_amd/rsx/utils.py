@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 MODELS = {"lightgcn": ("rsx.lightgcn", "LightGCN"), "layergcn": ("rsx.layergcn", "LayerGCN"),
-          "smore": ("rsx.smore", "SMORE")}
+          "smore": ("rsx.smore", "SMORE"), "bpr": ("rsx.bpr", "BPR"), "vbpr": ("rsx.vbpr", "VBPR")}
 
 
 def get_local_time():

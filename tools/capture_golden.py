@@ -15,7 +15,7 @@ modifies a reference file:
 Outputs are small `.npz` files under `tests/golden/` (data only: inputs and the
 reference's outputs). The reference itself never travels to the GPU box.
 
-Usage:  python tools/capture_golden.py [--out tests/golden]
+Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf]
 """
 from __future__ import annotations
 
@@ -220,7 +220,7 @@ def capture_model(model_name: str, dataset: str, overrides: dict, out_path: str,
     return ("done", out, config, hp)
 
 
-def capture_model_full(model_name, dataset, overrides, out_path, epochs, extra=None):
+def capture_model_full(model_name, dataset, overrides, out_path, epochs, extra=None, post=None):
     """Two passes with identical seeds: pass 1 captures first-step internals, pass 2 runs
     `epochs` reference epochs through `Trainer._train_epoch` and evaluates after each."""
     from utils.utils import init_seed, get_model
@@ -268,6 +268,8 @@ def capture_model_full(model_name, dataset, overrides, out_path, epochs, extra=N
     out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()])
     out["meta"] = np.array([f"torch={torch.__version__}", f"numpy={np.__version__}",
                             f"python={platform.python_version()}", "ref=/root/reference@2025-10-03"])
+    if post is not None:  # what is stored of the captured arrays (capture_mf: a smaller file)
+        out = post(out)
     np.savez_compressed(out_path, **out)
     print(f"wrote {out_path}: {os.path.getsize(out_path) / 1e6:.2f} MB, keys={len(out)}")
     return out
@@ -352,14 +354,57 @@ def capture_smore_d128(out_dir):
         torch.Tensor.cuda = orig_cuda
 
 
+def _mf_extra(model, out, tag):
+    if tag == "pre" and getattr(model, "v_feat", None) is not None:
+        out["v_feat"] = model.v_feat.numpy().copy()
+        out["t_feat"] = model.t_feat.numpy().copy()
+
+
+def _mf_stored(arrays):
+    """What capture_mf stores, every committed file under 1 MiB: no dense scores, no initial
+    evaluation, and the parameters after the first step as `step0_param_xor.*`, the XOR of
+    their f32 bit patterns with `init.*` (mostly zero high bits; tests/mf_ref.load_fixture
+    undoes it, bit-exact).  Otherwise the layout of lightgcn_small.npz."""
+    keep = {}
+    for k, v in arrays.items():
+        if k.endswith(("_scores", "_topk_val")) or k.startswith("init_valid_"):
+            continue
+        if k.startswith("step0_param."):
+            name = k[len("step0_param."):]
+            keep["step0_param_xor." + name] = v.view(np.int32) ^ arrays["init." + name].view(np.int32)
+            continue
+        keep[k] = v
+    return keep
+
+
+def capture_mf(out_dir):
+    """BPR and VBPR (reference src/models/bpr.py, vbpr.py) on the small graph of the other
+    fixtures: seed 999, the first value of every hyper-parameter list, VBPR on the SMORE
+    fixture's synthetic 48 / 24-wide features.  Data only, laid out as lightgcn_small.npz
+    without the dense score matrices and the initial evaluation."""
+    df = synth.amazon_like(400, 200, 4000, seed=7)
+    synth.write_inter(df, DATA_ROOT, "baby")
+    n_items = int(df.itemID.max()) + 1
+    np.save(os.path.join(DATA_ROOT, "baby", "image_feat_raw.npy"), synth.features(n_items, 48, seed=11))
+    np.save(os.path.join(DATA_ROOT, "baby", "text_feat_raw.npy"), synth.features(n_items, 24, seed=12))
+    common = dict(train_batch_size=512, eval_batch_size=256)
+    capture_model_full("BPR", "baby", dict(common, is_multimodal_model=False),
+                       os.path.join(out_dir, "bpr_small.npz"), epochs=3, post=_mf_stored)
+    capture_model_full("VBPR", "baby", dict(common, is_multimodal_model=True),
+                       os.path.join(out_dir, "vbpr_small.npz"), epochs=2, extra=_mf_extra, post=_mf_stored)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128")
+    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     _install_shims()
     shutil.rmtree(DATA_ROOT, ignore_errors=True)
+    if args.only == "mf":
+        capture_mf(args.out)
+        return
     if args.only in (None, "smore_d128"):
         capture_smore_d128(args.out)
     if args.only == "smore_d128":
