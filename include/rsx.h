@@ -1294,6 +1294,67 @@ int rsx_mf_step(const rsx_mf_step_args* st, rsx_stream_t stream);
  */
 int rsx_mf_loss_grad(const rsx_mf_step_args* st, float* gU, float* gI, float* gW, float* gb, rsx_stream_t stream);
 
+/*
+ * The bootstrap loss of BM3 (reference src/models/bm3.py:99-149 with
+ * src/common/loss.py:38-51), no negatives:
+ *   x_u = E[u],  x_i = E[n_users + i] + H[i],  x_t = T[i],  x_v = V[i]      (bm3.py:97,104-106)
+ *   target_s = keep_s(x_s) / (1 - p_drop)        four dropout streams      (bm3.py:108-121)
+ *   q_s = x_s P^T + pb                           the predictor             (bm3.py:123,133,139)
+ *   loss = (1 - mean cos(q_u, target_i)) + (1 - mean cos(q_i, target_u))   (bm3.py:145-146)
+ *        + cl_weight ((1 - mean cos(q_t, target_i)) + (1 - mean cos(q_v, target_i))   (:136,142)
+ *                   + (1 - mean cos(q_t, target_t)) + (1 - mean cos(q_v, target_v)))  (:137,143)
+ *        + reg_weight (|E_U|_F + |E_I + H|_F) / n_items   over the WHOLE tables (:148, loss.py:46-50)
+ * cos as torch.nn.functional.cosine_similarity: each norm clamped from below at 1e-8, so an
+ * all-dropped target row gives 0.  The targets carry no gradient.
+ *   E [n_users + n_items, d] the propagated mean table, H [n_items, d] the item-id table,
+ *   T, V [n_items, d] the projected text / image features (either or both NULL: their terms
+ *   are absent), P [d, d], pb [d], users / items int64 [batch].
+ *   keep_s: mask[s] (s = 0 user, 1 item, 2 text, 3 image) is a bit mask over the stream's
+ *   TABLE, one bit per element, row-major, d / 32 uint32 words a row, bit (c & 31) of word
+ *   c / 32 set = column c kept.  mask[s] NULL: with p_drop > 0 the element is kept when a
+ *   hash of (*seed, s, table row, column) is >= p_drop 2^32 (the convention of the fused
+ *   SMORE preference block), with p_drop = 0 every element is kept.  Either way a row that
+ *   occurs twice in a batch sees one mask.  seed: device int64 [1], read by the kernels
+ *   (advance it on the device between captured steps); may be NULL when no stream is hashed.
+ * rsx_bm3_loss_fwd writes out[0] = loss and out[1..7] = the terms ui, iu, t, v, tv, vt (each
+ * 1 - mean cos; 0 when absent) and the unweighted regulariser.  Deterministic: block
+ * partials added in index order.
+ * rsx_bm3_loss_bwd, after rsx_bm3_loss_fwd with the same arguments and the workspace it
+ * left, given the upstream gradient go (device f32 [1]): gP [d, d], gpb [d] (the fixed-order
+ * split reduction of rsx_linear_rows_wgrad), gE [n_users + n_items, d] written in full: the
+ * dense regulariser gradient go reg_weight / n_items * X / |X|_F on every row plus, on the
+ * batch's rows, the gradient pushed back through the cosines and the predictor; gT, gV
+ * [n_items, d] (with T / V) written in full, zero off the batch.  The gradient of H is
+ * gE[n_users:].  Repeated rows are accumulated with f32 atomics (as rsx_bpr's scatter), so
+ * gE, gT, gV are not bit-reproducible from run to run.
+ * A user or item index outside its table makes the loss NaN and scatters nothing.
+ * ws >= rsx_bm3_ws_bytes(batch, d), which does not decrease with batch.  d in {32, 64, 128},
+ * any batch >= 1, else RSX_ERR_UNSUPPORTED.
+ */
+typedef struct rsx_bm3_args {
+    int64_t n_users, n_items;
+    int32_t d, pad0;
+    const float* E; const float* H; const float* T; const float* V;
+    const float* P; const float* pb;
+    const int64_t* users; const int64_t* items;
+    int64_t batch;
+    float reg_weight, cl_weight, p_drop;
+    int32_t pad1;
+    const int64_t* seed;
+    const uint32_t* mask[4];
+    void* ws; size_t ws_bytes;
+} rsx_bm3_args;
+
+size_t rsx_bm3_ws_bytes(int64_t batch, int32_t d);
+int rsx_bm3_loss_fwd(const rsx_bm3_args* a, float* out, rsx_stream_t stream);
+/* The dropout targets alone: out [S batch, d], S = 2 + (T != NULL) + (V != NULL), the rows
+ * stacked by stream (user, item, text, image), row s batch + b = keep_s(x_s) / (1 - p_drop)
+ * of batch row b: what the cosines compare with (the masks made visible; overwrites the
+ * workspace's online rows, so not between a forward and its backward). */
+int rsx_bm3_targets(const rsx_bm3_args* a, float* out, rsx_stream_t stream);
+int rsx_bm3_loss_bwd(const rsx_bm3_args* a, const float* go, float* gE, float* gT, float* gV, float* gP, float* gpb,
+                     rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

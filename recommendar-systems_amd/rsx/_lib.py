@@ -116,6 +116,13 @@ class MfStep(C.Structure):
                 ("step_dev", P)]
 
 
+class Bm3Args(C.Structure):
+    _fields_ = [("n_users", I64), ("n_items", I64), ("d", I32), ("pad0", I32), ("E", P), ("H", P), ("T", P), ("V", P),
+                ("P", P), ("pb", P), ("users", P), ("items", P), ("batch", I64), ("reg_weight", F32),
+                ("cl_weight", F32), ("p_drop", F32), ("pad1", I32), ("seed", P), ("mask", P * 4), ("ws", P),
+                ("ws_bytes", C.c_size_t)]
+
+
 RSX_COLL_ALLREDUCE, RSX_COLL_ALLGATHER, RSX_COLL_REDUCESCATTER = 0, 1, 2
 RSX_COLL_F32, RSX_COLL_I64 = 0, 1
 HOST_COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, I32, P, I64, I32, P)
@@ -226,6 +233,10 @@ def _declare(lib):
         "rsx_mf_ws_bytes": (C.c_size_t, [I64, I32, I32]),
         "rsx_mf_step": (C.c_int, [C.POINTER(MfStep), P]),
         "rsx_mf_loss_grad": (C.c_int, [C.POINTER(MfStep), P, P, P, P, P]),
+        "rsx_bm3_ws_bytes": (C.c_size_t, [I64, I32]),
+        "rsx_bm3_loss_fwd": (C.c_int, [C.POINTER(Bm3Args), P, P]),
+        "rsx_bm3_targets": (C.c_int, [C.POINTER(Bm3Args), P, P]),
+        "rsx_bm3_loss_bwd": (C.c_int, [C.POINTER(Bm3Args), P, P, P, P, P, P, P]),
         "rsx_cpu_spmm": (C.c_int, [P, P, P, I64, P, I32, P]),
         "rsx_cpu_propagate_mean": (C.c_int, [P, P, P, I64, P, I32, I32, P]),
         "rsx_cpu_layergcn_forward": (C.c_int, [P, P, P, I64, P, I32, I32, P, P, P]),
@@ -262,7 +273,8 @@ EXPORTED = ["rsx_version", "rsx_csr_schedule_host", "rsx_csr_schedule_rebind", "
             "rsx_axpy_multi", "rsx_knn_ws_bytes", "rsx_knn_graph", "rsx_adj_build_ws_bytes", "rsx_adj_build",
             "rsx_edge_dropout_ws_bytes", "rsx_edge_dropout_build", "rsx_nan_gate",
             "rsx_linear_rows_fwd", "rsx_linear_rows_wgrad_ws_bytes", "rsx_linear_rows_wgrad", "rsx_mf_ws_bytes",
-            "rsx_mf_step", "rsx_mf_loss_grad",
+            "rsx_mf_step", "rsx_mf_loss_grad", "rsx_bm3_ws_bytes", "rsx_bm3_loss_fwd", "rsx_bm3_loss_bwd",
+            "rsx_bm3_targets",
             "rsx_cpu_spmm", "rsx_cpu_propagate_mean", "rsx_cpu_layergcn_forward", "rsx_cpu_layergcn_backward",
             "rsx_cpu_bpr", "rsx_cpu_fullsort_topk", "rsx_cpu_adam", "rsx_cpu_gcn_step_ws_floats", "rsx_cpu_gcn_step"]
 

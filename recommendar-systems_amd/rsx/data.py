@@ -147,7 +147,9 @@ class _Loader:
 
 
 class TrainDataLoader(_Loader):
-    """Training batches: LongTensor [3, B] = (user, positive item, negative item) on the device."""
+    """Training batches: LongTensor [3, B] = (user, positive item, negative item) on the device;
+    with `use_neg_sampling: False` (the bootstrap models: reference dataloader.py:124-130,
+    252-262) [2, B] = (user, item), the same stream without the negatives."""
 
     def __init__(self, config, dataset, batch_size=1, shuffle=False):
         super().__init__(config, dataset, batch_size, shuffle)
@@ -158,6 +160,8 @@ class TrainDataLoader(_Loader):
         self.sampler_kind = (config.get("rsx_sampler", "device") or "device").lower()
         if torch.device(self.device).type == "cpu":  # the CPU configuration: the reference's own host stream
             self.sampler_kind = "host"
+        # absent or True: triplets; False: (user, item) pairs
+        self.use_neg_sampling = config.get("use_neg_sampling", True) is not False
         self.history_items_per_u = {u: set(g.values) for u, g in df.groupby(dataset.uid_field)[dataset.iid_field]}
         self._dev_sampler = None
         self._epoch = -1
@@ -209,6 +213,8 @@ class TrainDataLoader(_Loader):
         self.pr += self.step
         users = part[self.dataset.uid_field].values
         items = part[self.dataset.iid_field].values
+        if not self.use_neg_sampling:  # reference _get_non_neg_sample: the shuffled table's slice
+            return torch.from_numpy(np.vstack([users, items]).astype(np.int64)).to(self.device)
         negs = []
         for u in users:
             x = random.sample(self.all_items, 1)[0]
@@ -232,7 +238,8 @@ class TrainDataLoader(_Loader):
             self._epoch_buf = s.sample_epoch(self._epoch, self.step, out=None)
         j = self.pr // self.step
         self.pr += self.step
-        return ops.DeviceSampler.batch_view(self._epoch_buf, s.n_inter, self.step, j)
+        trip = ops.DeviceSampler.batch_view(self._epoch_buf, s.n_inter, self.step, j)
+        return trip if self.use_neg_sampling else trip[:2]  # the epoch shuffle without the negative row
 
 
 class EvalDataLoader(_Loader):

@@ -9,7 +9,8 @@ import numpy as np
 import torch
 
 MODELS = {"lightgcn": ("rsx.lightgcn", "LightGCN"), "layergcn": ("rsx.layergcn", "LayerGCN"),
-          "smore": ("rsx.smore", "SMORE"), "bpr": ("rsx.bpr", "BPR"), "vbpr": ("rsx.vbpr", "VBPR")}
+          "smore": ("rsx.smore", "SMORE"), "bpr": ("rsx.bpr", "BPR"), "vbpr": ("rsx.vbpr", "VBPR"),
+          "bm3": ("rsx.bm3", "BM3")}
 
 
 def get_local_time():

@@ -15,7 +15,7 @@ modifies a reference file:
 Outputs are small `.npz` files under `tests/golden/` (data only: inputs and the
 reference's outputs). The reference itself never travels to the GPU box.
 
-Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf]
+Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3]
 """
 from __future__ import annotations
 
@@ -394,16 +394,140 @@ def capture_mf(out_dir):
                        os.path.join(out_dir, "vbpr_small.npz"), epochs=2, extra=_mf_extra, post=_mf_stored)
 
 
+def _pack_keep(keep: np.ndarray) -> np.ndarray:
+    """bool [n, d] -> uint32 [n, d / 32]: bit (c & 31) of word c // 32 = column c kept."""
+    n, d = keep.shape
+    bits = keep.reshape(n, d // 32, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)
+    return bits.sum(-1).astype(np.uint32)
+
+
+def _bm3_extra(model, out, tag):
+    if tag != "pre":
+        return
+    A = model.norm_adj.coalesce()
+    out["adj_idx"] = A.indices().numpy().astype(np.int32)
+    out["adj_val"] = A.values().numpy().astype(np.float32)
+    out["v_feat"] = model.v_feat.numpy().copy()
+    out["t_feat"] = model.t_feat.numpy().copy()
+
+
+def _bm3_stored(arrays):
+    """bm3_small.npz: vbpr_small.npz's layout (_mf_stored) with the [2, B] batches under
+    `epoch{e}_pairs`, the final parameters as `epoch{e}_param_xor.*` (XOR with `init.*`) and
+    without the first-step internals (bm3_step0_small.npz has its own)."""
+    keep = {}
+    for k, v in _mf_stored(arrays).items():
+        if k.startswith("step0_"):
+            continue
+        if k.endswith("_triplets"):
+            keep[k[: -len("_triplets")] + "_pairs"] = v.astype(np.int16)
+        elif "_param." in k:
+            ep, name = k.split("_param.")
+            keep[f"{ep}_param_xor.{name}"] = v.view(np.int32) ^ arrays["init." + name].view(np.int32)
+        elif k in ("init.image_embedding.weight", "init.text_embedding.weight"):
+            continue  # v_feat / t_feat, bit for bit (asserted below)
+        else:
+            keep[k] = v
+    assert np.array_equal(arrays["init.image_embedding.weight"], arrays["v_feat"])
+    assert np.array_equal(arrays["init.text_embedding.weight"], arrays["t_feat"])
+    return keep
+
+
+def capture_bm3(out_dir):
+    """BM3 (reference src/models/bm3.py) on the small graph and the 48 / 24-wide synthetic
+    features of the other fixtures, seed 999, embedding_size 64.
+    bm3_step0_small.npz: n_layers 2, dropout 0.3, reg_weight 0.1, cl_weight 2.0: the initial
+    parameters, the first batch's pairs, the four keep masks F.dropout drew (user, item,
+    text, image tables; packed), the loss, its seven terms and every parameter's gradient.
+    bm3_small.npz: n_layers 1, dropout 0.0: two epochs through the reference's Trainer with
+    batches of 512 (the last one of an epoch is short), laid out as vbpr_small.npz."""
+    import torch.nn.functional as F
+    from torch.nn.functional import cosine_similarity
+
+    df = synth.amazon_like(400, 200, 4000, seed=7)
+    synth.write_inter(df, DATA_ROOT, "baby")
+    n_items = int(df.itemID.max()) + 1
+    np.save(os.path.join(DATA_ROOT, "baby", "image_feat_raw.npy"), synth.features(n_items, 48, seed=11))
+    np.save(os.path.join(DATA_ROOT, "baby", "text_feat_raw.npy"), synth.features(n_items, 24, seed=12))
+    common = dict(train_batch_size=512, eval_batch_size=256, is_multimodal_model=True)
+
+    # ---- the first step, with the masks torch drew
+    from utils.utils import init_seed, get_model
+
+    over = dict(common, n_layers=[2], dropout=[0.3], reg_weight=[0.1], cl_weight=2.0)
+    config, train, _, _ = _load("BM3", "baby", over)
+    hp = _select_hparams(config)
+    init_seed(config["seed"])
+    train.pretrain_setup()
+    model = get_model("BM3")(config, train)
+    out = {"n_users": np.int64(model.n_users), "n_items": np.int64(model.n_items)}
+    inter = train.inter_matrix(form="coo")
+    out["train_u"], out["train_i"] = inter.row.astype(np.int64), inter.col.astype(np.int64)
+    _bm3_extra(model, out, "pre")
+    for n, p in _param_dict(model).items():
+        if n not in ("image_embedding.weight", "text_embedding.weight"):  # v_feat / t_feat
+            out["init." + n] = p.numpy()
+    batch = next(iter(train))
+    keeps = []
+    orig = F.dropout
+
+    def recording(x, p=0.5, training=True, inplace=False):
+        y = orig(x, p, training, inplace)
+        keeps.append((y != 0) | (x == 0))  # a zero input: kept or not makes no difference
+        return y
+
+    F.dropout = recording
+    try:
+        model.train()
+        loss = model.calculate_loss(batch)
+    finally:
+        F.dropout = orig
+    loss.backward()
+    assert len(keeps) == 4
+    for name, k in zip(("user", "item", "text", "image"), keeps):
+        out["keep_" + name] = _pack_keep(k.numpy())
+    out["pairs"] = batch.numpy().astype(np.int16)
+    out["step0_loss"] = np.float64(loss.item())
+    for n, p in model.named_parameters():
+        out["step0_grad." + n] = p.grad.numpy().copy()
+    # the seven terms, restated with the recorded masks (their weighted sum is the loss)
+    with torch.no_grad():
+        u, i = model.forward()
+        t = model.text_trs(model.text_embedding.weight)
+        v = model.image_trs(model.image_embedding.weight)
+        us, it = batch[0], batch[1]
+        tg = [x * k / (1 - 0.3) for x, k in zip((u, i, t, v), keeps)]
+        pr = model.predictor
+        cosm = lambda a, b: float(1 - cosine_similarity(a, b, dim=-1).mean())  # noqa: E731
+        terms = [cosm(pr(u)[us], tg[1][it]), cosm(pr(i)[it], tg[0][us]), cosm(pr(t)[it], tg[1][it]),
+                 cosm(pr(v)[it], tg[1][it]), cosm(pr(t)[it], tg[2][it]), cosm(pr(v)[it], tg[3][it]),
+                 float(model.reg_loss(u, i))]
+    total = terms[0] + terms[1] + 0.1 * terms[6] + 2.0 * sum(terms[2:6])
+    assert abs(total - loss.item()) <= 1e-5 * abs(loss.item()), (total, loss.item())
+    out["step0_terms"] = np.array(terms, dtype=np.float64)
+    out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()] + ["cl_weight=2.0"])
+    path = os.path.join(out_dir, "bm3_step0_small.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}: {os.path.getsize(path) / 1e6:.2f} MB, keys={len(out)}")
+
+    # ---- two epochs through the reference's Trainer
+    capture_model_full("BM3", "baby", dict(common, n_layers=[1], dropout=[0.0], reg_weight=[0.1], cl_weight=2.0),
+                       os.path.join(out_dir, "bm3_small.npz"), epochs=2, extra=_bm3_extra, post=_bm3_stored)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf")
+    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     _install_shims()
     shutil.rmtree(DATA_ROOT, ignore_errors=True)
     if args.only == "mf":
         capture_mf(args.out)
+        return
+    if args.only == "bm3":
+        capture_bm3(args.out)
         return
     if args.only in (None, "smore_d128"):
         capture_smore_d128(args.out)
