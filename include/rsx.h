@@ -1355,6 +1355,54 @@ int rsx_bm3_targets(const rsx_bm3_args* a, float* out, rsx_stream_t stream);
 int rsx_bm3_loss_bwd(const rsx_bm3_args* a, const float* go, float* gE, float* gT, float* gV, float* gP, float* gpb,
                      rsx_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* MGCN per-row blocks (mgcn.hip)                                            */
+/* ------------------------------------------------------------------------ */
+/*
+ * Behaviour-guided purifier (reference src/models/mgcn.py:152-154), m = image, text:
+ *   forward  (backward = 0): out[m] = item * sigmoid(feat[m] W[m]^T + b[m]); rows [n, d],
+ *            W [d, d].
+ *   backward (backward = 1): given gout[m] (NULL = zero) writes g_item, g_feat[m] and
+ *            dz[m] = d pre-activation (dW = dz^T feat, db = colsum dz: rsx_smore_wgrad).
+ * d in {64, 128} (else RSX_ERR_UNSUPPORTED); n = 0 is RSX_OK.  Caller-owned buffers, no
+ * allocation or synchronisation; stream-ordered and graph-capturable.
+ */
+int rsx_mgcn_purify(int32_t backward, const float* const* feat, const float* item, const float* const* W,
+                    const float* const* b, int64_t n, int32_t d, float* const* out, const float* const* gout,
+                    float* g_item, float* const* g_feat, float* const* dz, rsx_stream_t stream);
+/*
+ * Behaviour-aware fuser (reference src/models/mgcn.py:187-201).  W[4] / b[4]:
+ * query_common.0 [d, d], query_common.2 [1, d] (no bias: b[1] ignored),
+ * gate_image_prefer.0, gate_text_prefer.0.  Per logical row r < n, with C / I / T the
+ * rows of content / image_emb / text_emb at rows[r] (rows = NULL: at r; n <= n_table):
+ *   aX = w2 . tanh(W1 X + b1), X = I, T;  (wI, wT) = softmax(aI, aT);  cm = wI I + wT T
+ *   pI = sigmoid(Wip C + bip), pT = sigmoid(Wtp C + btp)
+ *   side = (pI (I - cm) + pT (T - cm) + cm) / 3;  all = C + side
+ *   forward:  writes all_out, side_out [n, d] and, where given, the gathered
+ *             content_out / text_out rows.
+ *   backward: from g_all, g_side (NULL = zero) and g_content_in (NULL = zero; the gradient
+ *             of content_out) writes g_content, g_image, g_text -- [n, d] rows with
+ *             rows = NULL, else whole [n_table, d] tables (zero off `rows`, repeated rows
+ *             summed per table row in ascending occurrence order: deterministic) --, the
+ *             gradient rows dz[4] [n, d] for rsx_smore_wgrad and dw2 [d] (an ordered
+ *             reduction).  d aT = -d aI exactly, so W1's two pre-activation gradient row
+ *             sets (on I and on T) nearly cancel where I ~ T; they are written as
+ *             dz[0] = dz1I with the input rows dif_out = I - T and dz[1] = dz1I + dz1T
+ *             (formed as d aI w2 (hT - hI)(hT + hI)) with the input rows T:
+ *             dW1 = dz[0]^T dif_out + dz[1]^T T, db1 = colsum dz[1].  dz[2], dz[3]: Wip,
+ *             Wtp (input rows C).  The forward's activations are recomputed.
+ *             ws: rsx_mgcn_fuse_ws_bytes(n, n_table, d, rows != NULL) bytes.
+ * d in {64, 128} (else RSX_ERR_UNSUPPORTED); n = 0 is RSX_OK.  No allocation or
+ * synchronisation; stream-ordered and graph-capturable.
+ */
+size_t rsx_mgcn_fuse_ws_bytes(int64_t n, int64_t n_table, int32_t d, int32_t rows_form);
+int rsx_mgcn_fuse(int32_t backward, const float* const* W, const float* const* b, const float* content,
+                  const float* image_emb, const float* text_emb, const int64_t* rows, int64_t n, int64_t n_table,
+                  int32_t d, float* all_out, float* side_out, float* content_out, float* text_out,
+                  const float* g_all, const float* g_side, const float* g_content_in, float* g_content,
+                  float* g_image, float* g_text, float* const* dz, float* dif_out, float* dw2, void* ws,
+                  size_t ws_bytes, rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

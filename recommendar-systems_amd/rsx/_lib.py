@@ -237,6 +237,10 @@ def _declare(lib):
         "rsx_bm3_loss_fwd": (C.c_int, [C.POINTER(Bm3Args), P, P]),
         "rsx_bm3_targets": (C.c_int, [C.POINTER(Bm3Args), P, P]),
         "rsx_bm3_loss_bwd": (C.c_int, [C.POINTER(Bm3Args), P, P, P, P, P, P, P]),
+        "rsx_mgcn_purify": (C.c_int, [I32, P, P, P, P, I64, I32, P, P, P, P, P, P]),
+        "rsx_mgcn_fuse_ws_bytes": (C.c_size_t, [I64, I64, I32, I32]),
+        "rsx_mgcn_fuse": (C.c_int, [I32, P, P, P, P, P, P, I64, I64, I32, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
+                                    C.c_size_t, P]),
         "rsx_cpu_spmm": (C.c_int, [P, P, P, I64, P, I32, P]),
         "rsx_cpu_propagate_mean": (C.c_int, [P, P, P, I64, P, I32, I32, P]),
         "rsx_cpu_layergcn_forward": (C.c_int, [P, P, P, I64, P, I32, I32, P, P, P]),
@@ -274,7 +278,7 @@ EXPORTED = ["rsx_version", "rsx_csr_schedule_host", "rsx_csr_schedule_rebind", "
             "rsx_edge_dropout_ws_bytes", "rsx_edge_dropout_build", "rsx_nan_gate",
             "rsx_linear_rows_fwd", "rsx_linear_rows_wgrad_ws_bytes", "rsx_linear_rows_wgrad", "rsx_mf_ws_bytes",
             "rsx_mf_step", "rsx_mf_loss_grad", "rsx_bm3_ws_bytes", "rsx_bm3_loss_fwd", "rsx_bm3_loss_bwd",
-            "rsx_bm3_targets",
+            "rsx_bm3_targets", "rsx_mgcn_purify", "rsx_mgcn_fuse_ws_bytes", "rsx_mgcn_fuse",
             "rsx_cpu_spmm", "rsx_cpu_propagate_mean", "rsx_cpu_layergcn_forward", "rsx_cpu_layergcn_backward",
             "rsx_cpu_bpr", "rsx_cpu_fullsort_topk", "rsx_cpu_adam", "rsx_cpu_gcn_step_ws_floats", "rsx_cpu_gcn_step"]
 

@@ -9,13 +9,14 @@ modifies a reference file:
    imported by `src/utils/dataset.py:17`) is replaced by an empty module;
 2. `str()` is called on each split so that `RecDataset.inter_num` exists
    (`src/utils/dataset.py:115`, needed at `src/utils/dataloader.py:55`);
-3. `torch.Tensor.cuda` is the identity while SMORE is built (`src/models/smore.py:63,73`);
+3. `torch.Tensor.cuda` is the identity while SMORE or MGCN is built (`src/models/smore.py:63,73`,
+   `src/models/mgcn.py:59,69`);
 4. `torch_scatter.scatter_add` is restated with `index_add_` (`src/utils/utils.py:140`).
 
 Outputs are small `.npz` files under `tests/golden/` (data only: inputs and the
 reference's outputs). The reference itself never travels to the GPU box.
 
-Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3]
+Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn]
 """
 from __future__ import annotations
 
@@ -515,14 +516,94 @@ def capture_bm3(out_dir):
                        os.path.join(out_dir, "bm3_small.npz"), epochs=2, extra=_bm3_extra, post=_bm3_stored)
 
 
+def _mgcn_extra(model, out, tag):
+    if tag != "pre":
+        return
+    for name in ("norm_adj", "R", "image_original_adj", "text_original_adj"):
+        A = getattr(model, name).coalesce()
+        out[f"{name}_idx"] = A.indices().numpy().astype(np.int16 if max(A.shape) < 32768 else np.int32)
+        out[f"{name}_val"] = A.values().numpy().astype(np.float32)
+    with torch.no_grad():
+        model.eval()
+        u, i, side, content = model.forward(model.norm_adj, train=True)
+        out["fwd_user"], out["fwd_item"] = u.numpy(), i.numpy()
+        out["fwd_side"], out["fwd_content"] = side.numpy(), content.numpy()
+    model.train()
+    out["v_feat"] = model.v_feat.numpy().copy()
+    out["t_feat"] = model.t_feat.numpy().copy()
+
+
+def _mgcn_stored(step0_path):
+    """mgcn_small.npz: the four graphs, the eval-mode forward and the epochs in bm3_small.npz's
+    layout (parameters as XOR with `init.*`, triplets as int16) and, written here,
+    mgcn_step0_small.npz: the initial parameters and the first step.  Not stored: v_feat / t_feat
+    (smore_small.npz holds the same arrays) and init.{image,text}_embedding.weight (= them)."""
+
+    def post(arrays):
+        assert np.array_equal(arrays["init.image_embedding.weight"], arrays["v_feat"])
+        assert np.array_equal(arrays["init.text_embedding.weight"], arrays["t_feat"])
+        ref = np.load(os.path.join(os.path.dirname(step0_path), "smore_small.npz"))
+        assert np.array_equal(ref["v_feat"], arrays["v_feat"]) and np.array_equal(ref["t_feat"], arrays["t_feat"])
+        step0, epochs = {}, {}
+        for k, v in _mf_stored(arrays).items():
+            if k in ("v_feat", "t_feat", "init.image_embedding.weight", "init.text_embedding.weight"):
+                continue
+            if k.startswith(("init.", "step0_")):
+                step0[k] = v
+            elif k.endswith("_triplets"):
+                epochs[k] = v.astype(np.int16)
+            elif "_param." in k:
+                ep, name = k.split("_param.")
+                epochs[f"{ep}_param_xor.{name}"] = v.view(np.int32) ^ arrays["init." + name].view(np.int32)
+            else:
+                epochs[k] = v
+        for k in ("n_users", "n_items", "hparams", "meta"):
+            step0[k] = arrays[k]
+        step0["step0_triplets"] = arrays["epoch0_triplets"][:, :512].astype(np.int16)  # the first batch
+        np.savez_compressed(step0_path, **step0)
+        print(f"wrote {step0_path}: {os.path.getsize(step0_path) / 1e6:.2f} MB, keys={len(step0)}")
+        return epochs
+
+    return post
+
+
+def capture_mgcn(out_dir):
+    """MGCN (reference src/models/mgcn.py) on the small graph and the 48 / 24-wide synthetic
+    features of the other fixtures: seed 999, the YAML defaults with cl_loss 0.01, batches of
+    512, two epochs through the reference's Trainer.  The dataset directory is emptied
+    first: the reference caches its kNN graphs there ({image,text}_adj_10_True.pt) and
+    would load a SMORE capture's."""
+    shutil.rmtree(os.path.join(DATA_ROOT, "baby"), ignore_errors=True)
+    df = synth.amazon_like(400, 200, 4000, seed=7)
+    synth.write_inter(df, DATA_ROOT, "baby")
+    n_items = int(df.itemID.max()) + 1
+    np.save(os.path.join(DATA_ROOT, "baby", "image_feat_raw.npy"), synth.features(n_items, 48, seed=11))
+    np.save(os.path.join(DATA_ROOT, "baby", "text_feat_raw.npy"), synth.features(n_items, 24, seed=12))
+
+    orig_cuda = torch.Tensor.cuda
+    torch.Tensor.cuda = lambda self, *a, **k: self  # mgcn.py:59,69
+    try:
+        capture_model_full("MGCN", "baby",
+                           dict(train_batch_size=512, eval_batch_size=256, is_multimodal_model=True, cl_loss=[0.01]),
+                           os.path.join(out_dir, "mgcn_small.npz"), epochs=2, extra=_mgcn_extra,
+                           post=_mgcn_stored(os.path.join(out_dir, "mgcn_step0_small.npz")))
+    finally:
+        torch.Tensor.cuda = orig_cuda
+    for f in ("mgcn_small.npz", "mgcn_step0_small.npz"):
+        assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3")
+    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     _install_shims()
     shutil.rmtree(DATA_ROOT, ignore_errors=True)
+    if args.only == "mgcn":
+        capture_mgcn(args.out)
+        return
     if args.only == "mf":
         capture_mf(args.out)
         return
