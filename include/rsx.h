@@ -1403,6 +1403,49 @@ int rsx_mgcn_fuse(int32_t backward, const float* const* W, const float* const* b
                   float* g_image, float* g_text, float* const* dz, float* dif_out, float* dw2, void* ws,
                   size_t ws_bytes, rsx_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* FREEDOM training loss (freedom.hip)                                       */
+/* ------------------------------------------------------------------------ */
+/*
+ * Three BPR terms that share the user row (reference src/models/freedom.py:182-212).  Per
+ * triplet (u, i, j) of the batch, with e_u = E[u], e_i = E[n_users + i] + H[i] (H NULL: no
+ * second term), x_id = sum(e_u * e_i) - sum(e_u * e_j), x_t = sum(e_u * T[i]) - sum(e_u * T[j]),
+ * x_v likewise on V:
+ *   id = mean softplus(-x_id), text = mean softplus(-x_t), image = mean softplus(-x_v)
+ *   total = id + reg (text + image)            a NULL table's term is 0; not both NULL
+ * softplus(-x) = max(-x, 0) + log1p(exp(-|x|)) (F.logsigmoid's form).
+ * rsx_freedom_loss_fwd writes out[0..3] = total, id, text, image: block partials added in
+ * index order, no atomics.
+ * rsx_freedom_loss_bwd, given the upstream gradient go (device f32 [1], read on the device),
+ * writes EVERY row of gE [n_users + n_items, d] and, with T / V, of gT / gV [n_items, d]:
+ * zero off the batch's rows; a user row holds the sum over its triplets of all three terms'
+ * contributions, an item row of gE the id term's, of gT / gV the feature terms'.  The
+ * gradient of H is gE[n_users:].  Rows repeated in the batch (an item that is a positive
+ * here and a negative there included) are summed in an order fixed by the triplets alone:
+ * no float atomics, bit-identical from run to run.  The backward recomputes the scores: it
+ * needs nothing the forward left in ws.
+ * A triplet with an index outside its table makes the loss NaN and contributes no gradient.
+ * ws >= rsx_freedom_ws_bytes(batch, d) bytes (0 for an unsupported shape).  d in {64, 128},
+ * 1 <= batch <= 65536 (the backward's walk over the batch's keys is quadratic in batch),
+ * tables below 2^31 rows, else RSX_ERR_UNSUPPORTED; batch < 1, a NULL E / triplets / ws, T and
+ * V both NULL or a pointer that is not 16-byte aligned: RSX_ERR_ARG.  No allocation or
+ * synchronisation; stream-ordered and graph-capturable.
+ */
+typedef struct rsx_freedom_args {
+    const float* E;          /* [n_users + n_items, d] mean-propagated [U; I] table; read on the batch rows only */
+    const float* H;          /* [n_items, d] mm_adj^L item_id table, or NULL */
+    const float* T;          /* [n_items, d] text_trs(text_embedding), or NULL */
+    const float* V;          /* [n_items, d] image_trs(image_embedding), or NULL */
+    const int64_t* triplets; /* [3, batch] users, positives, negatives (item ids, not offset) */
+    int64_t n_users, n_items, batch;
+    int32_t d;               /* 64 or 128 */
+    float reg;               /* weight of the feature terms */
+} rsx_freedom_args;
+size_t rsx_freedom_ws_bytes(int64_t batch, int32_t d);
+int rsx_freedom_loss_fwd(const rsx_freedom_args* a, float* out, void* ws, size_t ws_bytes, rsx_stream_t stream);
+int rsx_freedom_loss_bwd(const rsx_freedom_args* a, const float* go, float* gE, float* gT, float* gV, void* ws,
+                         size_t ws_bytes, rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

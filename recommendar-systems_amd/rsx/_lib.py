@@ -123,6 +123,11 @@ class Bm3Args(C.Structure):
                 ("ws_bytes", C.c_size_t)]
 
 
+class FreedomArgs(C.Structure):
+    _fields_ = [("E", P), ("H", P), ("T", P), ("V", P), ("triplets", P), ("n_users", I64), ("n_items", I64),
+                ("batch", I64), ("d", I32), ("reg", F32)]
+
+
 RSX_COLL_ALLREDUCE, RSX_COLL_ALLGATHER, RSX_COLL_REDUCESCATTER = 0, 1, 2
 RSX_COLL_F32, RSX_COLL_I64 = 0, 1
 HOST_COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, I32, P, I64, I32, P)
@@ -241,6 +246,9 @@ def _declare(lib):
         "rsx_mgcn_fuse_ws_bytes": (C.c_size_t, [I64, I64, I32, I32]),
         "rsx_mgcn_fuse": (C.c_int, [I32, P, P, P, P, P, P, I64, I64, I32, P, P, P, P, P, P, P, P, P, P, P, P, P, P,
                                     C.c_size_t, P]),
+        "rsx_freedom_ws_bytes": (C.c_size_t, [I64, I32]),
+        "rsx_freedom_loss_fwd": (C.c_int, [C.POINTER(FreedomArgs), P, P, C.c_size_t, P]),
+        "rsx_freedom_loss_bwd": (C.c_int, [C.POINTER(FreedomArgs), P, P, P, P, P, C.c_size_t, P]),
         "rsx_cpu_spmm": (C.c_int, [P, P, P, I64, P, I32, P]),
         "rsx_cpu_propagate_mean": (C.c_int, [P, P, P, I64, P, I32, I32, P]),
         "rsx_cpu_layergcn_forward": (C.c_int, [P, P, P, I64, P, I32, I32, P, P, P]),
@@ -279,6 +287,7 @@ EXPORTED = ["rsx_version", "rsx_csr_schedule_host", "rsx_csr_schedule_rebind", "
             "rsx_linear_rows_fwd", "rsx_linear_rows_wgrad_ws_bytes", "rsx_linear_rows_wgrad", "rsx_mf_ws_bytes",
             "rsx_mf_step", "rsx_mf_loss_grad", "rsx_bm3_ws_bytes", "rsx_bm3_loss_fwd", "rsx_bm3_loss_bwd",
             "rsx_bm3_targets", "rsx_mgcn_purify", "rsx_mgcn_fuse_ws_bytes", "rsx_mgcn_fuse",
+            "rsx_freedom_ws_bytes", "rsx_freedom_loss_fwd", "rsx_freedom_loss_bwd",
             "rsx_cpu_spmm", "rsx_cpu_propagate_mean", "rsx_cpu_layergcn_forward", "rsx_cpu_layergcn_backward",
             "rsx_cpu_bpr", "rsx_cpu_fullsort_topk", "rsx_cpu_adam", "rsx_cpu_gcn_step_ws_floats", "rsx_cpu_gcn_step"]
 

@@ -10,7 +10,8 @@ import torch
 
 MODELS = {"lightgcn": ("rsx.lightgcn", "LightGCN"), "layergcn": ("rsx.layergcn", "LayerGCN"),
           "smore": ("rsx.smore", "SMORE"), "bpr": ("rsx.bpr", "BPR"), "vbpr": ("rsx.vbpr", "VBPR"),
-          "bm3": ("rsx.bm3", "BM3"), "mgcn": ("rsx.mgcn", "MGCN")}
+          "bm3": ("rsx.bm3", "BM3"), "mgcn": ("rsx.mgcn", "MGCN"),
+          "freedom": ("rsx.freedom", "FREEDOM")}
 
 
 def get_local_time():

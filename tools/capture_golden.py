@@ -16,7 +16,7 @@ modifies a reference file:
 Outputs are small `.npz` files under `tests/golden/` (data only: inputs and the
 reference's outputs). The reference itself never travels to the GPU box.
 
-Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn]
+Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom]
 """
 from __future__ import annotations
 
@@ -593,16 +593,72 @@ def capture_mgcn(out_dir):
         assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
 
 
+def _freedom_extra(model, out, tag):
+    if tag == "pre":
+        for name in ("mm_adj", "norm_adj"):
+            A = getattr(model, name).coalesce()
+            out[f"{name}_idx"] = A.indices().numpy().astype(np.int16 if max(A.shape) < 32768 else np.int32)
+            out[f"{name}_val"] = A.values().numpy().astype(np.float32)
+        out["edge_idx"] = model.edge_indices.numpy().astype(np.int16)
+        with torch.no_grad():
+            model.eval()
+            u, i = model.forward(model.norm_adj)
+            out["fwd_user"], out["fwd_item"] = u.numpy(), i.numpy()
+        model.train()
+        out["v_feat"] = model.v_feat.numpy().copy()
+        out["t_feat"] = model.t_feat.numpy().copy()
+    elif tag.startswith("e") and not tag.startswith("epoch"):
+        # the epoch's kept edges, read back from masked_adj (its first half is the kept
+        # (user, n_users + item) pairs in drawn order) as a bit mask over the training edges
+        A = model.masked_adj
+        half = A._indices().shape[1] // 2
+        kept = A._indices()[:, :half].numpy()
+        ei = model.edge_indices.numpy()
+        eid = {(int(a), int(b)): k for k, (a, b) in enumerate(zip(ei[0], ei[1]))}
+        ids = np.array([eid[(int(a), int(b) - model.n_users)] for a, b in zip(kept[0], kept[1])])
+        mask = np.zeros(ei.shape[1], dtype=bool)
+        mask[ids] = True
+        assert int(mask.sum()) == half == int(ei.shape[1] * (1.0 - model.dropout))
+        out[f"{tag}_keep"] = np.packbits(mask)
+        out[f"{tag}_masked_val"] = A.coalesce().values().numpy().astype(np.float32)
+
+
+def capture_freedom(out_dir):
+    """FREEDOM (reference src/models/freedom.py) on the small graph and the 48 / 24-wide
+    synthetic features of the other fixtures: seed 999, dropout 0.8, reg_weight 0.001 (the
+    YAML's first value, 0.0, switches the feature terms off), batches of 512, two epochs
+    through the reference's Trainer.  The dataset directory is emptied first.  Stored as
+    capture_mgcn stores (freedom_small.npz, freedom_step0_small.npz), plus mm_adj, norm_adj,
+    the eval-mode forward, the training edges and, per epoch, the kept edges (a packed bit
+    mask over the training edges) and the coalesced masked_adj values."""
+    shutil.rmtree(os.path.join(DATA_ROOT, "baby"), ignore_errors=True)
+    df = synth.amazon_like(400, 200, 4000, seed=7)
+    synth.write_inter(df, DATA_ROOT, "baby")
+    n_items = int(df.itemID.max()) + 1
+    np.save(os.path.join(DATA_ROOT, "baby", "image_feat_raw.npy"), synth.features(n_items, 48, seed=11))
+    np.save(os.path.join(DATA_ROOT, "baby", "text_feat_raw.npy"), synth.features(n_items, 24, seed=12))
+    capture_model_full("FREEDOM", "baby",
+                       dict(train_batch_size=512, eval_batch_size=256, is_multimodal_model=True, dropout=[0.8],
+                            reg_weight=[0.001]),
+                       os.path.join(out_dir, "freedom_small.npz"), epochs=2, extra=_freedom_extra,
+                       post=_mgcn_stored(os.path.join(out_dir, "freedom_step0_small.npz")))
+    for f in ("freedom_small.npz", "freedom_step0_small.npz"):
+        assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn")
+    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     _install_shims()
     shutil.rmtree(DATA_ROOT, ignore_errors=True)
     if args.only == "mgcn":
         capture_mgcn(args.out)
+        return
+    if args.only == "freedom":
+        capture_freedom(args.out)
         return
     if args.only == "mf":
         capture_mf(args.out)
