@@ -1446,6 +1446,90 @@ int rsx_freedom_loss_fwd(const rsx_freedom_args* a, float* out, void* ws, size_t
 int rsx_freedom_loss_bwd(const rsx_freedom_args* a, const float* go, float* gE, float* gT, float* gV, void* ws,
                          size_t ws_bytes, rsx_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* LATTICE: training loss and learned item graph (lattice.hip)               */
+/* ------------------------------------------------------------------------ */
+/*
+ * The loss (reference src/models/lattice.py:199-227).  Per triplet (u, i, j) of the batch, with
+ * e_u = E[u], e_i = E[n_users + i] + H[i] / max(|H[i]|, 1e-12) (F.normalize), x = <e_u, e_i> - <e_u, e_j>:
+ *   mf = mean softplus(-x), emb = reg * sum 1/2 (|e_u|^2 + |e_i|^2 + |e_j|^2) / batch_size
+ * batch_size is the configured one, not `batch`.  rsx_lattice_loss_fwd writes out[0..2] =
+ * mf + emb, mf, emb: block partials added in index order, no atomics.
+ * rsx_lattice_loss_bwd, given the upstream gradient go (device f32 [1]), writes EVERY row of
+ * gE [n_users + n_items, d] and gH [n_items, d]: zero off the batch's rows; an item row of gH is
+ * the row's gE sent through the normalise Jacobian (g - hn <hn, g>) / max(|h|, 1e-12).  Rows
+ * repeated in the batch are summed in an order fixed by the triplets alone (freedom.hip's
+ * first-occurrence walk): no float atomics, bit-identical from run to run.  The backward
+ * recomputes the scores: it needs nothing the forward left in ws.
+ * A triplet with an index outside its table makes the loss NaN and contributes no gradient.
+ * ws >= rsx_lattice_ws_bytes(batch, d) bytes (0 for an unsupported shape).  d in {64, 128},
+ * 1 <= batch <= 65536, tables below 2^31 rows, else RSX_ERR_UNSUPPORTED; a NULL E / H /
+ * triplets / ws, batch_size <= 0 or a pointer that is not 16-byte aligned: RSX_ERR_ARG.  No
+ * allocation or synchronisation; stream-ordered and graph-capturable.
+ */
+typedef struct rsx_lattice_args {
+    const float* E;          /* [n_users + n_items, d] the backbone's table; read on the batch rows only */
+    const float* H;          /* [n_items, d] item_adj^n_layers item_id table */
+    const int64_t* triplets; /* [3, batch] users, positives, negatives (item ids, not offset) */
+    int64_t n_users, n_items, batch;
+    int32_t d;               /* 64 or 128 */
+    float reg;               /* reg_weight */
+    float batch_size;        /* train_batch_size */
+    int32_t pad0;
+} rsx_lattice_args;
+size_t rsx_lattice_ws_bytes(int64_t batch, int32_t d);
+int rsx_lattice_loss_fwd(const rsx_lattice_args* a, float* out, void* ws, size_t ws_bytes, rsx_stream_t stream);
+int rsx_lattice_loss_bwd(const rsx_lattice_args* a, const float* go, float* gE, float* gH, void* ws,
+                         size_t ws_bytes, rsx_stream_t stream);
+
+/*
+ * The learned item graph (lattice.py:137-163) without the dense [n, n] matrices.  With
+ * w = softmax(modal_weight) (n_mod = 1: w = 1), a_m[i, j] = cos(F_m[i], F_m[idx_m[i, j]]),
+ * r_i = sum_m w_m sum_j a_m[i, j], dis = r^-1/2 (inf -> 0), O_m = (oidx_m, oval_m):
+ *   (item_adj x)_i = (1 - lambda) dis_i sum_m w_m sum_j a_m[i, j] dis_c x_c + lambda sum_m w_m sum_j O_m[i, j] x_c'
+ * kept as one edge table col / val [n, K], K = 2 n_mod k: slots [m k, (m + 1) k) are modality
+ * m's learned list, slots [(n_mod + m) k, ...) its original list (repeated columns of a row
+ * stay unmerged).  A column outside [0, n) is an edge of weight 0.
+ * rsx_lattice_graph reads F, idx, oidx, oval, modal_weight, lambda and writes w, invn
+ * (1 / |F_m[i]|), a, r, dis, col, val; nothing is read on the host.
+ * The transpose is an index the caller builds from col once per build: tedge = the edge ids
+ * (row K + slot) sorted by column, equal columns in edge order, tptr [n + 1] its row pointer.
+ * rsx_lattice_prop: y = item_adj x (transpose 0) or item_adj^T x (transpose 1; needs
+ * tptr / tedge); x != y, [n, d], d in {64, 128}.
+ * rsx_lattice_graph_bwd: the build batch's backward.  G[l] / X[l] (host arrays of n_layers <= 4
+ * device tables [n, d]) are the gradient at the output and the input of item layer l.  Writes
+ * gF0 / gF1 [n, f], the gradients of the projected features (through both cosine
+ * normalisations), and g_modal_weight [2] (n_mod = 2).  Column-side sums go through the
+ * transpose index; deterministic, no float atomics.  ws >= rsx_lattice_graph_bwd_ws_bytes.
+ * f in {64, 128}, k <= 32, k <= n, else RSX_ERR_UNSUPPORTED.  No allocation or synchronisation.
+ */
+typedef struct rsx_lattice_graph_args {
+    int64_t n;                /* items */
+    int32_t k, n_mod, f;      /* list length, modalities (1 or 2), feat_embed_dim (64 or 128) */
+    float lambda;             /* lambda_coeff */
+    const float* F[2];        /* [n, f] projected features */
+    const int64_t* idx[2];    /* [n, k] learned top-k columns */
+    const int64_t* oidx[2];   /* [n, k] original graph's columns */
+    const float* oval[2];     /* [n, k] original graph's normalised values */
+    const float* modal_weight; /* [2] raw weights, NULL when n_mod == 1 */
+    float* w;                 /* [2] out: softmax(modal_weight) */
+    float* invn[2];           /* [n] out */
+    float* a[2];              /* [n, k] out: the kept cosine similarities */
+    float* r;                 /* [n] out */
+    float* dis;               /* [n] out */
+    int32_t* col;             /* [n, K] out */
+    float* val;               /* [n, K] out */
+    const int64_t* tptr;      /* [n + 1] transpose row pointer (caller-built) */
+    const int32_t* tedge;     /* [n K] edge ids by column (caller-built) */
+} rsx_lattice_graph_args;
+int rsx_lattice_graph(const rsx_lattice_graph_args* g, rsx_stream_t stream);
+int rsx_lattice_prop(const rsx_lattice_graph_args* g, const float* x, float* y, int32_t d, int32_t transpose,
+                     rsx_stream_t stream);
+size_t rsx_lattice_graph_bwd_ws_bytes(int64_t n, int32_t k, int32_t n_mod);
+int rsx_lattice_graph_bwd(const rsx_lattice_graph_args* g, int32_t n_layers, const float* const* G,
+                          const float* const* X, int32_t d, float* gF0, float* gF1, float* g_modal_weight,
+                          void* ws, size_t ws_bytes, rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

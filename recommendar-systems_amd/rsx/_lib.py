@@ -128,6 +128,17 @@ class FreedomArgs(C.Structure):
                 ("batch", I64), ("d", I32), ("reg", F32)]
 
 
+class LatticeArgs(C.Structure):
+    _fields_ = [("E", P), ("H", P), ("triplets", P), ("n_users", I64), ("n_items", I64), ("batch", I64),
+                ("d", I32), ("reg", F32), ("batch_size", F32), ("pad0", I32)]
+
+
+class LatticeGraph(C.Structure):
+    _fields_ = [("n", I64), ("k", I32), ("n_mod", I32), ("f", I32), ("lam", F32), ("F", P * 2), ("idx", P * 2),
+                ("oidx", P * 2), ("oval", P * 2), ("modal_weight", P), ("w", P), ("invn", P * 2), ("a", P * 2),
+                ("r", P), ("dis", P), ("col", P), ("val", P), ("tptr", P), ("tedge", P)]
+
+
 RSX_COLL_ALLREDUCE, RSX_COLL_ALLGATHER, RSX_COLL_REDUCESCATTER = 0, 1, 2
 RSX_COLL_F32, RSX_COLL_I64 = 0, 1
 HOST_COLLECTIVE_FN = C.CFUNCTYPE(C.c_int, I32, P, I64, I32, P)
@@ -249,6 +260,13 @@ def _declare(lib):
         "rsx_freedom_ws_bytes": (C.c_size_t, [I64, I32]),
         "rsx_freedom_loss_fwd": (C.c_int, [C.POINTER(FreedomArgs), P, P, C.c_size_t, P]),
         "rsx_freedom_loss_bwd": (C.c_int, [C.POINTER(FreedomArgs), P, P, P, P, P, C.c_size_t, P]),
+        "rsx_lattice_ws_bytes": (C.c_size_t, [I64, I32]),
+        "rsx_lattice_loss_fwd": (C.c_int, [C.POINTER(LatticeArgs), P, P, C.c_size_t, P]),
+        "rsx_lattice_loss_bwd": (C.c_int, [C.POINTER(LatticeArgs), P, P, P, P, C.c_size_t, P]),
+        "rsx_lattice_graph": (C.c_int, [C.POINTER(LatticeGraph), P]),
+        "rsx_lattice_prop": (C.c_int, [C.POINTER(LatticeGraph), P, P, I32, I32, P]),
+        "rsx_lattice_graph_bwd_ws_bytes": (C.c_size_t, [I64, I32, I32]),
+        "rsx_lattice_graph_bwd": (C.c_int, [C.POINTER(LatticeGraph), I32, P, P, I32, P, P, P, P, C.c_size_t, P]),
         "rsx_cpu_spmm": (C.c_int, [P, P, P, I64, P, I32, P]),
         "rsx_cpu_propagate_mean": (C.c_int, [P, P, P, I64, P, I32, I32, P]),
         "rsx_cpu_layergcn_forward": (C.c_int, [P, P, P, I64, P, I32, I32, P, P, P]),
@@ -288,6 +306,8 @@ EXPORTED = ["rsx_version", "rsx_csr_schedule_host", "rsx_csr_schedule_rebind", "
             "rsx_mf_step", "rsx_mf_loss_grad", "rsx_bm3_ws_bytes", "rsx_bm3_loss_fwd", "rsx_bm3_loss_bwd",
             "rsx_bm3_targets", "rsx_mgcn_purify", "rsx_mgcn_fuse_ws_bytes", "rsx_mgcn_fuse",
             "rsx_freedom_ws_bytes", "rsx_freedom_loss_fwd", "rsx_freedom_loss_bwd",
+            "rsx_lattice_ws_bytes", "rsx_lattice_loss_fwd", "rsx_lattice_loss_bwd", "rsx_lattice_graph",
+            "rsx_lattice_prop", "rsx_lattice_graph_bwd_ws_bytes", "rsx_lattice_graph_bwd",
             "rsx_cpu_spmm", "rsx_cpu_propagate_mean", "rsx_cpu_layergcn_forward", "rsx_cpu_layergcn_backward",
             "rsx_cpu_bpr", "rsx_cpu_fullsort_topk", "rsx_cpu_adam", "rsx_cpu_gcn_step_ws_floats", "rsx_cpu_gcn_step"]
 

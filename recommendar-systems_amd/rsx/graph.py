@@ -71,6 +71,22 @@ def layergcn_masked_adj(e_u: np.ndarray, e_i: np.ndarray, n_users: int, n_items:
     return to_csr(rows, cols, v, n, n)
 
 
+def lattice_norm_adj(train_u: np.ndarray, train_i: np.ndarray, n_users: int, n_items: int):
+    """LATTICE's row-normalised UI adjacency with self loops, D^-1 (A + I), as scipy
+    computes it (lattice.py:100-122: np.power(rowsum, -1), cast to float32 at :126).  Returns
+    (rowptr, col, val, val_t): the CSR triple and, for the same structure (A + I is
+    symmetric), the values of the transpose: val_t at (r, c) is the matrix's value at (c, r)."""
+    n = n_users + n_items
+    rows, cols = _sym_edges(train_u, train_i, n_users)
+    loops = np.arange(n, dtype=np.int64)
+    rows, cols = np.concatenate([rows, loops]), np.concatenate([cols, loops])
+    # adj + sp.eye is float64 in scipy, so the reciprocal is taken in float64 and rounded once
+    deg = np.bincount(rows, minlength=n).astype(np.float64)
+    dinv = np.power(deg, -1).astype(np.float32)  # deg >= 1: the self loop
+    rowptr, col, val = to_csr(rows, cols, dinv[rows], n, n)
+    return rowptr, col, val, dinv[col.astype(np.int64)].astype(np.float32)
+
+
 def smore_norm_adj(train_u: np.ndarray, train_i: np.ndarray, n_users: int, n_items: int):
     """SMORE's float32 sym-normalised UI adjacency (no epsilon, inf -> 0); CSR triple."""
     n = n_users + n_items

@@ -70,16 +70,17 @@ def _prop_mean(A, x, K):
 
 
 class _PropMean(torch.autograd.Function):
-    """mean_{k=0..K} A^k x for a symmetric A (backward: the same operator)."""
+    """mean_{k=0..K} A^k x; the backward is the same mean on AT, the transposed operator
+    (None: A is symmetric and is its own transpose)."""
 
     @staticmethod
-    def forward(ctx, x, A, K):
-        ctx.A, ctx.K = A, K
+    def forward(ctx, x, A, K, AT=None):
+        ctx.AT, ctx.K = AT if AT is not None else A, K
         return _prop_mean(A, x, K)
 
     @staticmethod
     def backward(ctx, g):
-        return _prop_mean(ctx.A, g, ctx.K), None, None
+        return _prop_mean(ctx.AT, g, ctx.K), None, None, None
 
 
 class _Joined(torch.autograd.Function):
@@ -126,7 +127,8 @@ class _RowTags:
 
 
 class _PropMeanRows(torch.autograd.Function):
-    """mean_{k=0..K} A^k x for a symmetric A, needed at the tagged rows only (K <= 4;
+    """mean_{k=0..K} A^k x, needed at the tagged rows only, for a symmetric A or, with AT, for
+    an A whose transpose is the operator AT (the backward runs on AT) (K <= 4;
     the batch rows of the SMORE training loss): E^1..E^{K-1} stored (no running sum),
     the last layer and the mean on the tagged rows only, in the running sum's order
     (((E0 + E1) + E2) + E3) + A E3 (other rows of the output are left unwritten).  The
@@ -138,7 +140,7 @@ class _PropMeanRows(torch.autograd.Function):
     path's arithmetic: the same mean operator applied to G)."""
 
     @staticmethod
-    def forward(ctx, x, A, K, tags, rows=None):
+    def forward(ctx, x, A, K, tags, rows=None, AT=None):
         x = x.contiguous()
         n, d = x.shape
         out = torch.empty_like(x)
@@ -151,7 +153,8 @@ class _PropMeanRows(torch.autograd.Function):
         e = ops.epi(L.RSX_EPI_FINAL, beta=1.0 / (K + 1), f=out, row_tag=tags.row_tag, tag_dev=tags.tag_dev, **stored)
         e.tag_flags = L.RSX_TAG_ROWS
         A.spmm_epi(cur, e, d)
-        ctx.A, ctx.K, ctx.tags, ctx.rows = A, K, tags, rows
+        # ctx.A: the backward's operator
+        ctx.A, ctx.K, ctx.tags, ctx.rows = AT if AT is not None else A, K, tags, rows
         return out
 
     @staticmethod
@@ -172,7 +175,7 @@ class _PropMeanRows(torch.autograd.Function):
             e.tag_flags = L.RSX_TAG_SPARSE_S | (L.RSX_TAG_SPARSE_X if k == 1 else 0)
             A.spmm_epi(h, e, d)
             h = y
-        return h, None, None, None, None
+        return h, None, None, None, None, None
 
 
 def knn_graph(feat: np.ndarray, k: int):

@@ -103,6 +103,10 @@ class _GraphStep:
     def _kind(self):
         """(mirror-gradient batch?) or None when the batch must run eagerly."""
         m = self.t.model
+        # a model may keep single batches out of the graphs (optional hook `graph_step_eager`:
+        # LATTICE's once-per-epoch item-graph build)
+        if getattr(m, "graph_step_eager", lambda: False)():
+            return None
         g1 = int(getattr(m, "global_step", 0)) + 1  # the step id _mirror_gradient will see
         log_every = int(getattr(m, "mg_log_interval", 50))
         if log_every > 0 and g1 % log_every == 0 and hasattr(m, "log_mm_diagnostics"):

@@ -9,14 +9,14 @@ modifies a reference file:
    imported by `src/utils/dataset.py:17`) is replaced by an empty module;
 2. `str()` is called on each split so that `RecDataset.inter_num` exists
    (`src/utils/dataset.py:115`, needed at `src/utils/dataloader.py:55`);
-3. `torch.Tensor.cuda` is the identity while SMORE or MGCN is built (`src/models/smore.py:63,73`,
-   `src/models/mgcn.py:59,69`);
+3. `torch.Tensor.cuda` is the identity while SMORE, MGCN or LATTICE is built (`src/models/smore.py:63,73`,
+   `src/models/mgcn.py:59,69`, `src/models/lattice.py:76,87`);
 4. `torch_scatter.scatter_add` is restated with `index_add_` (`src/utils/utils.py:140`).
 
 Outputs are small `.npz` files under `tests/golden/` (data only: inputs and the
 reference's outputs). The reference itself never travels to the GPU box.
 
-Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom]
+Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice]
 """
 from __future__ import annotations
 
@@ -646,10 +646,209 @@ def capture_freedom(out_dir):
         assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
 
 
+LATTICE_OVERRIDES = dict(train_batch_size=512, eval_batch_size=256, is_multimodal_model=True, reg_weight=[1e-3],
+                         learning_rate=[0.001], cf_model="lightgcn", knn_k=10, lambda_coeff=0.9, n_layers=1,
+                         weight_size=[64, 64])
+
+
+def _lattice_features(n_items: int, dim: int, seed: int) -> np.ndarray:
+    """Synthetic features in clusters of knn_k = 10 items (a seeded N(0,1) centre a cluster, plus
+    0.3 N(0,1) an item, the items dealt to the clusters by a seeded permutation): a row's 10th
+    and 11th similarities are then an in-cluster and an out-of-cluster one, far apart, in the raw
+    space and after a linear projection.  With synth.features' independent rows the smallest
+    of a build's 200 gaps measured 4e-6 .. 1e-4 over 60 seed pairs, so no seed meets the
+    capture's 1e-4 condition on all four builds."""
+    rng = np.random.default_rng(seed)
+    n_cl = max(n_items // 10, 1)
+    centre = rng.standard_normal((n_cl, dim))
+    member = rng.permutation(np.arange(n_items) % n_cl)
+    return (centre[member] + 0.3 * rng.standard_normal((n_items, dim))).astype(np.float32)
+
+
+class _KnnTap:
+    """Records every build_knn_neighbourhood call of models.lattice: the kept columns and each
+    row's gap between its k-th and (k+1)-th similarity.  `phase` names the next calls."""
+
+    def __init__(self):
+        import models.lattice as ml
+
+        self.ml, self.orig = ml, ml.build_knn_neighbourhood
+        self.phase, self.calls = "init", []
+
+        def tapped(adj, topk):
+            with torch.no_grad():
+                v, i = torch.topk(adj, min(topk + 1, adj.shape[1]), dim=-1)
+                gap = v[:, topk - 1] - v[:, topk] if v.shape[1] > topk else torch.full_like(v[:, 0], float("inf"))
+                _, kept = torch.topk(adj, topk, dim=-1)
+            self.calls.append((self.phase, kept.numpy().astype(np.int16), gap.numpy().astype(np.float32)))
+            return self.orig(adj, topk)
+
+        ml.build_knn_neighbourhood = tapped
+
+    def first(self, phase):
+        """The (image, text) records of the first build after `phase` was set."""
+        c = [x for x in self.calls if x[0] == phase]
+        assert len(c) >= 2, (phase, len(c))
+        return c[0], c[1]
+
+    def close(self):
+        self.ml.build_knn_neighbourhood = self.orig
+
+
+def _lattice_extra(tap):
+    def extra(model, out, tag):
+        if tag == "pre":
+            A = model.norm_adj.coalesce()
+            out["norm_adj_idx"] = A.indices().numpy().astype(np.int16)
+            out["norm_adj_val"] = A.values().numpy().astype(np.float32)
+            (_, iv, gi), (_, it, gt) = tap.first("init")  # the constructor's two original graphs
+            for name, idx, O in (("image", iv, model.image_original_adj), ("text", it, model.text_original_adj)):
+                out[f"orig_{name}_idx"] = idx
+                out[f"orig_{name}_val"] = torch.gather(O, 1, torch.from_numpy(idx.astype(np.int64))).numpy()
+                assert int((O != 0).sum()) == idx.size  # the lists are the whole graph
+            out["orig_image_gap"], out["orig_text_gap"] = gi, gt
+            tap.phase = "fwd"
+            with torch.no_grad():
+                model.eval()
+                u, i = model.forward(model.norm_adj, build_item_graph=True)
+                out["fwd_user"], out["fwd_item"] = u.numpy(), i.numpy()
+            out["_fwd_image_idx"], out["_fwd_text_idx"] = (c[1] for c in tap.first("fwd"))
+            model.train()
+            model.build_item_graph = True
+            model.item_adj = None
+            out["v_feat"] = model.v_feat.numpy().copy()
+            out["t_feat"] = model.t_feat.numpy().copy()
+        elif tag.startswith("e") and not tag.startswith("epoch"):
+            ep = int(tag[1:])
+            tap.phase = f"build{ep}"
+            if ep > 0:
+                for n, p in _param_dict(model).items():
+                    out[f"epoch{ep - 1}_param." + n] = p.numpy()
+
+    return extra
+
+
+def _lattice_two_steps(out):
+    """A third identically seeded run: the gradients (and which are None) after the first
+    batch, which builds the item graph, and after the second, which does not."""
+    from utils.utils import init_seed, get_model
+    from common.trainer import Trainer
+
+    config, train, _, _ = _load("LATTICE", "baby", LATTICE_OVERRIDES)
+    _select_hparams(config)
+    init_seed(config["seed"])
+    train.pretrain_setup()
+    model = get_model("LATTICE")(config, train)
+    trainer = Trainer(config, model)
+    model.train()
+    model.pre_epoch_processing()
+    it = iter(train)
+    for s in (0, 1):
+        batch = next(it)
+        assert np.array_equal(batch.numpy(), out["epoch0_triplets"][:, 512 * s: 512 * (s + 1)])
+        trainer.optimizer.zero_grad()
+        loss = model.calculate_loss(batch)
+        loss.backward()
+        out[f"step{s}_loss"] = np.float64(loss.item())
+        none = []
+        for n, p in model.named_parameters():
+            if p.grad is None:
+                none.append(n)
+            else:
+                out[f"step{s}_grad." + n] = p.grad.numpy().copy()
+        out[f"step{s}_none"] = np.array(none)
+        trainer.optimizer.step()
+        for n, p in _param_dict(model).items():
+            out[f"step{s}_param." + n] = p.numpy()
+
+
+def _lattice_stored(step0_path, tap):
+    """lattice_small.npz: the graphs, the builds' neighbours and gaps, the eval-mode forward and
+    the epochs (parameters as XOR with `init.*`, triplets as int16); lattice_step0_small.npz: the
+    initial parameters and the first two steps (parameters as XOR likewise).  Not stored:
+    init.{image,text}_embedding.weight (= v_feat / t_feat, which lattice_small.npz holds)."""
+
+    def post(arrays):
+        assert np.array_equal(arrays["init.image_embedding.weight"], arrays["v_feat"])
+        assert np.array_equal(arrays["init.text_embedding.weight"], arrays["t_feat"])
+        gaps = []
+        for ep in (0, 1):
+            for name, (_, idx, gap) in zip(("image", "text"), tap.first(f"build{ep}")):
+                arrays[f"build{ep}_{name}_idx"], arrays[f"build{ep}_{name}_gap"] = idx, gap
+                gaps.append(float(gap.min()))
+        # the initial parameters' build, in evaluation as in the first batch
+        assert np.array_equal(arrays.pop("_fwd_image_idx"), arrays["build0_image_idx"])
+        assert np.array_equal(arrays.pop("_fwd_text_idx"), arrays["build0_text_idx"])
+        _lattice_two_steps(arrays)
+        print(f"smallest k-th / (k+1)-th gaps of the builds: {gaps}")
+        assert min(gaps) >= 1e-4, "a row's neighbour set is within 1e-4 of a tie: change the feature seed"
+        step0, epochs = {}, {}
+        for k, v in arrays.items():
+            if k in ("init.image_embedding.weight", "init.text_embedding.weight"):
+                continue
+            if k.endswith("_scores") or k.endswith("_topk_val"):
+                continue
+            if "_param." in k:
+                pre, name = k.split("_param.")
+                v = v.view(np.int32) ^ arrays["init." + name].view(np.int32)
+                k = f"{pre}_param_xor.{name}"
+            if k.startswith(("init.", "step0_", "step1_")):
+                step0[k] = v
+            elif k.endswith("_triplets"):
+                epochs[k] = v.astype(np.int16)
+            else:
+                epochs[k] = v
+        for k in ("n_users", "n_items", "hparams", "meta"):
+            step0[k] = arrays[k]
+        np.savez_compressed(step0_path, **step0)
+        print(f"wrote {step0_path}: {os.path.getsize(step0_path) / 1e6:.2f} MB, keys={len(step0)}")
+        return epochs
+
+    return post
+
+
+def capture_lattice(out_dir):
+    """LATTICE (reference src/models/lattice.py) on the small graph and 48 / 24-wide synthetic
+    features of its own (_lattice_features): seed 999, cf_model lightgcn, knn_k 10, lambda 0.9, one item
+    layer, reg_weight 1e-3, learning rate 1e-3, batches of 512, two epochs through the
+    reference's Trainer.  The dataset directory is emptied first (the reference caches its
+    original graphs there)."""
+    shutil.rmtree(os.path.join(DATA_ROOT, "baby"), ignore_errors=True)
+    df = synth.amazon_like(400, 200, 4000, seed=7)
+    synth.write_inter(df, DATA_ROOT, "baby")
+    n_items = int(df.itemID.max()) + 1
+    np.save(os.path.join(DATA_ROOT, "baby", "image_feat_raw.npy"), _lattice_features(n_items, 48, seed=11))
+    np.save(os.path.join(DATA_ROOT, "baby", "text_feat_raw.npy"), _lattice_features(n_items, 24, seed=12))
+
+    orig_cuda = torch.Tensor.cuda
+    torch.Tensor.cuda = lambda self, *a, **k: self  # lattice.py:76,87
+    tap = _KnnTap()
+    real_load = _load
+
+    def fresh_load(*a, **k):  # every pass builds its original graphs itself: no cache file is read
+        for f in ("image_adj_10.pt", "text_adj_10.pt"):
+            if os.path.exists(os.path.join(DATA_ROOT, "baby", f)):
+                os.remove(os.path.join(DATA_ROOT, "baby", f))
+        tap.phase, tap.calls = "init", []
+        return real_load(*a, **k)
+
+    globals()["_load"] = fresh_load
+    try:
+        capture_model_full("LATTICE", "baby", LATTICE_OVERRIDES, os.path.join(out_dir, "lattice_small.npz"),
+                           epochs=2, extra=_lattice_extra(tap),
+                           post=_lattice_stored(os.path.join(out_dir, "lattice_step0_small.npz"), tap))
+    finally:
+        globals()["_load"] = real_load
+        torch.Tensor.cuda = orig_cuda
+        tap.close()
+    for f in ("lattice_small.npz", "lattice_step0_small.npz"):
+        assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom")
+    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     _install_shims()
@@ -659,6 +858,9 @@ def main():
         return
     if args.only == "freedom":
         capture_freedom(args.out)
+        return
+    if args.only == "lattice":
+        capture_lattice(args.out)
         return
     if args.only == "mf":
         capture_mf(args.out)
