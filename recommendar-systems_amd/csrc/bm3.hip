@@ -337,8 +337,6 @@ __global__ __launch_bounds__(256) void scatter(Args a, const float* __restrict__
     atomicAdd(dst + c, dX[r * D + c]);
 }
 
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // the workspace: X, Q, G, dX [4 B, d], P^T [d, d], the loss partials, the norm partials, the
 // two norms, rsx_linear_rows_wgrad's workspace; every size grows with B
 struct Ws {
@@ -349,25 +347,19 @@ struct Ws {
 };
 inline Ws carve(void* ws, int64_t B, int d) {
     Ws w;
-    char* p = static_cast<char*>(ws);
-    size_t o = 0;
-    const size_t rows = al((size_t)4 * (size_t)B * d * sizeof(float));
-    auto take = [&](size_t n) {
-        char* q = p ? p + o : nullptr;
-        o += al(n);
-        return q;
-    };
-    w.X = reinterpret_cast<float*>(take(rows));
-    w.Q = reinterpret_cast<float*>(take(rows));
-    w.G = reinterpret_cast<float*>(take(rows));
-    w.dX = reinterpret_cast<float*>(take(rows));
-    w.PT = reinterpret_cast<float*>(take((size_t)d * d * sizeof(float)));
-    w.part = reinterpret_cast<float*>(take(((size_t)B / 8 + 1) * 8 * sizeof(float)));
-    w.rpart = reinterpret_cast<double*>(take((size_t)kRegBlocks * 2 * sizeof(double)));
-    w.norms = reinterpret_cast<float*>(take(4 * sizeof(float)));
+    Carver cv(ws);
+    const size_t rows = (size_t)4 * (size_t)B * d * sizeof(float);
+    w.X = cv.take<float>(rows);
+    w.Q = cv.take<float>(rows);
+    w.G = cv.take<float>(rows);
+    w.dX = cv.take<float>(rows);
+    w.PT = cv.take<float>((size_t)d * d * sizeof(float));
+    w.part = cv.take<float>(((size_t)B / 8 + 1) * 8 * sizeof(float));
+    w.rpart = cv.take<double>((size_t)kRegBlocks * 2 * sizeof(double));
+    w.norms = cv.take<float>(4 * sizeof(float));
     w.wg_bytes = rsx_linear_rows_wgrad_ws_bytes(4 * B, d, d);
-    w.wg = take(w.wg_bytes);
-    w.total = o;
+    w.wg = cv.take<void>(w.wg_bytes);
+    w.total = cv.total();
     return w;
 }
 

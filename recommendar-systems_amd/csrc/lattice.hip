@@ -12,24 +12,23 @@
 // The dense matrix is never formed: item_adj is kept as 2 M lists of k edges a row (M
 // modalities: the learned top-k lists and the original graphs' lists), in which it is linear.
 //
-// Layout: a d-wide row is one lane group of L = d / 4 float4 lanes (freedom.hip's layout).
+// Layout: a d-wide row is one lane group of L = d / 4 float4 lanes (rsx_triplet.hpp's RowGeom).
 //
 // The loss.  Forward: loss_rows (a lane group a triplet, block partials in row order), finish
 //   (the partials in index order).  Backward: memsets, grad_rows (coefficient and user-row
-//   contribution of a triplet, the keys as int32), sum_rows: freedom.hip's first-occurrence
-//   walk (the wave of a destination's first occurrence adds the later ones in a fixed order),
-//   which also sends an item row's sum through the normalise Jacobian into gH.
+//   contribution of a triplet, the keys as int32), sum_rows: rsx_triplet.hpp's first-occurrence
+//   walk, which here also sends an item row's sum through the normalise Jacobian into gH.
 // The graph.  One edge table [n, K], K = 2 M k: slots [m k, (m + 1) k) the learned list of
 //   modality m, slots [(M + m) k, ...) its original list.  The transpose is an index: the edge
 //   ids sorted by column (stable, built by the caller once per epoch) with a row pointer; the
 //   values are read through it, so they exist once.  No float atomics anywhere: every sum is
 //   a walk of a row's slots or of a column's index segment in a fixed order.
-#include "rsx_common.hpp"
+#include "rsx_triplet.hpp"
 
 namespace rsx {
 namespace lattice {
 
-constexpr int64_t kMaxBatch = 65536;
+constexpr int kPartStride = 2, kCoef = 1;  // words a block partial, coefficients a triplet
 constexpr int kMaxLayers = 4;
 constexpr float kNormEps = 1e-12f;  // F.normalize's eps
 
@@ -40,15 +39,6 @@ struct Args {
     float reg, bs;
 };
 
-__device__ __forceinline__ float4 sub4(float4 a, float4 b) {
-    return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w);
-}
-__device__ __forceinline__ float softplus_neg(float x) { return fmaxf(-x, 0.f) + log1pf(expf(-fabsf(x))); }
-__device__ __forceinline__ float sigmoid_neg(float x) {
-    const float e = expf(-fabsf(x));
-    return x >= 0.f ? e / (1.f + e) : 1.f / (1.f + e);
-}
-
 // E[nu + i] + H[i] / max(|H[i]|, eps) as seen by one lane (its 4 columns)
 template <int D>
 __device__ __forceinline__ float4 item_row(const Args& a, int64_t i, int c) {
@@ -58,9 +48,7 @@ __device__ __forceinline__ float4 item_row(const Args& a, int64_t i, int c) {
 }
 
 template <int D>
-struct Trip {
-    bool ok;
-    int64_t u, p, n;
+struct Trip : TripIdx {
     float4 ur, pr, nr;
     float x;
 };
@@ -68,8 +56,7 @@ struct Trip {
 template <int D>
 __device__ __forceinline__ void load_trip(const Args& a, int64_t b, int c, Trip<D>& t) {
     constexpr int L = D / 4;
-    t.u = a.trip[b], t.p = a.trip[a.B + b], t.n = a.trip[2 * a.B + b];
-    t.ok = t.u >= 0 && t.u < a.nu && t.p >= 0 && t.p < a.ni && t.n >= 0 && t.n < a.ni;
+    load_idx(a.trip, a.B, b, a.nu, a.ni, t);
     t.ur = t.pr = t.nr = f4(0.f);
     if (!t.ok) {  // uniform over the row's lane group
         t.x = __builtin_nanf("");
@@ -84,38 +71,25 @@ __device__ __forceinline__ void load_trip(const Args& a, int64_t b, int c, Trip<
 // part[block] = {sum softplus(-x), sum 1/2 (|u|^2 + |p|^2 + |n|^2)} over the block's triplets, in row order
 template <int D>
 __global__ __launch_bounds__(256) void loss_rows(Args a, float* __restrict__ part) {
-    constexpr int L = D / 4, RPB = 256 / L;
-    __shared__ float sh[RPB][2];
-    const int lr = threadIdx.x / L, c = (threadIdx.x % L) * 4;
-    const int64_t b = (int64_t)blockIdx.x * RPB + lr;
+    constexpr int L = RowGeom<D>::L;
+    const RowGeom<D> r;
     float v[2] = {0.f, 0.f};
-    if (b < a.B) {  // uniform over a row's lane group
+    if (r.b < a.B) {  // uniform over a row's lane group
         Trip<D> t;
-        load_trip<D>(a, b, c, t);
+        load_trip<D>(a, r.b, r.c, t);
         v[0] = softplus_neg(t.x);
         const float sq = group_sum<L>(dot4(t.ur, t.ur)) + group_sum<L>(dot4(t.pr, t.pr)) +
                          group_sum<L>(dot4(t.nr, t.nr));
         v[1] = t.ok ? 0.5f * sq : __builtin_nanf("");
     }
-    if (c == 0) sh[lr][0] = v[0], sh[lr][1] = v[1];
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        float acc = 0.f;
-        for (int j = 0; j < RPB; ++j) acc += sh[j][threadIdx.x];
-        part[(int64_t)blockIdx.x * 2 + threadIdx.x] = acc;
-    }
+    block_partials<D, 2, kPartStride>(r, v, part);
 }
 
-// out = {total, mf, emb}
+// out = {total, mf, emb}: the block partials in index order
 __global__ __launch_bounds__(64) void finish(const float* __restrict__ part, int nblk, int64_t B, float reg, float bs,
                                              float* __restrict__ out) {
     float term[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        float acc = 0.f;
-        for (int j = threadIdx.x; j < nblk; j += kWave) acc += part[(int64_t)j * 2 + k];
-        term[k] = group_sum<kWave>(acc);
-    }
+    sum_partials<2, kPartStride>(part, nblk, term);
     if (threadIdx.x == 0) {
         const float mf = term[0] / (float)B, emb = reg * (term[1] / bs);
         out[0] = mf + emb;
@@ -125,14 +99,14 @@ __global__ __launch_bounds__(64) void finish(const float* __restrict__ part, int
 }
 
 // Per triplet b: coef[b] = d total / d x, occU[b] = its contribution to the user row
-// coef (p - n) + s u with s = go reg / batch_size, and the keys as int32 (-1: not counted).
+// coef (p - n) + s u with s = go reg / batch_size, and the keys (store_keys).
 template <int D>
 __global__ __launch_bounds__(256) void grad_rows(Args a, const float* __restrict__ go, float* __restrict__ occU,
                                                  float* __restrict__ coef, int32_t* __restrict__ ku,
                                                  int32_t* __restrict__ ki) {
-    constexpr int L = D / 4, RPB = 256 / L;
-    const int lr = threadIdx.x / L, c = (threadIdx.x % L) * 4;
-    const int64_t b = (int64_t)blockIdx.x * RPB + lr;
+    const RowGeom<D> r;
+    const int64_t b = r.b;
+    const int c = r.c;
     if (b >= a.B) return;  // uniform over a row's lane group
     Trip<D> t;
     load_trip<D>(a, b, c, t);
@@ -144,48 +118,28 @@ __global__ __launch_bounds__(256) void grad_rows(Args a, const float* __restrict
     st4(occU + b * D + c, fma4(s, t.ur, mul4(ck, sub4(t.pr, t.nr))));
     if (c == 0) {
         coef[b] = ck;
-        ku[b] = t.ok ? (int32_t)t.u : -1;
-        ki[b] = t.ok ? (int32_t)t.p : -1;
-        ki[a.B + b] = t.ok ? (int32_t)t.n : -1;
+        store_keys(t, a.B, b, ku, ki);
     }
 }
 
-// Which of the 256 keys at `base` (a multiple of 256) equal `key`, among the indices in
-// [lo, hi): lane l loads keys base + 4 l .. + 3 as one int4 (the key arrays are 256-byte
-// aligned and padded to a multiple of 64 entries), bit l of m[q] answers for base + 4 l + q.
-__device__ __forceinline__ void match256(const int32_t* __restrict__ keys, int64_t base, int lane, int64_t lo,
-                                         int64_t hi, int32_t key, unsigned long long m[4]) {
-    const int64_t i = base + 4 * lane;
-    int4 k = make_int4(-1, -1, -1, -1);
-    if (i < hi) k = *reinterpret_cast<const int4*>(keys + i);
-    m[0] = __ballot(i >= lo && i < hi && k.x == key);
-    m[1] = __ballot(i + 1 >= lo && i + 1 < hi && k.y == key);
-    m[2] = __ballot(i + 2 >= lo && i + 2 < hi && k.z == key);
-    m[3] = __ballot(i + 3 >= lo && i + 3 < hi && k.w == key);
-}
-
-// The per-destination sums.  Wave w < B: user occurrence w; else item occurrence w - B of
-// [positives; negatives].  An item row's sum g = sum(+-coef E[user]) + count s row goes to
-// gE[nu + key], and (g - hn <hn, g>) / max(|h|, eps), hn = h / max(|h|, eps), to gH[key].
+// The per-destination sums (rsx_triplet.hpp's walk).  Wave w < B: user occurrence w; else item
+// occurrence w - B of [positives; negatives].  An item row's sum g = sum(+-coef E[user]) +
+// count s row goes to gE[nu + key], and (g - hn <hn, g>) / max(|h|, eps), hn = h / max(|h|, eps),
+// to gH[key].
 template <int D>
 __global__ __launch_bounds__(256) void sum_rows(Args a, const float* __restrict__ go, const float* __restrict__ occU,
                                                 const float* __restrict__ coef, const int32_t* __restrict__ ku,
                                                 const int32_t* __restrict__ ki, float* __restrict__ gE,
                                                 float* __restrict__ gH) {
-    constexpr int L = D / 4, G = kWave / L, kChunk = 4 * kWave;
+    constexpr int L = RowGeom<D>::L;
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), B = a.B;
-    if (w >= 3 * B) return;  // wave-uniform, as every branch on w, j, key and the ballots below
+    if (w >= 3 * B) return;  // wave-uniform, as every branch on w, j and key below
     const bool user = w < B;
     const int32_t* __restrict__ keys = user ? ku : ki;
     const int64_t n = user ? B : 2 * B, j = user ? w : w - B;
     const int32_t key = keys[j];
-    if (key < 0) return;
-    unsigned long long m[4];
-    for (int64_t base = 0; base < j; base += kChunk) {  // an earlier occurrence leads
-        match256(keys, base, lane, 0, j, key, m);
-        if (m[0] | m[1] | m[2] | m[3]) return;
-    }
+    if (key < 0 || !leads(keys, j, key, lane)) return;
     const int g = lane / L, c = (lane % L) * 4;
     float4 hn = f4(0.f), sp = f4(0.f);
     float inv = 0.f;
@@ -196,39 +150,17 @@ __global__ __launch_bounds__(256) void sum_rows(Args a, const float* __restrict_
         sp = mul4(*go * a.reg / a.bs, add4(hn, ld4(a.E + (a.nu + key) * D + c)));
     }
     float4 acc = f4(0.f);
-    for (int64_t base = j & ~(int64_t)(kChunk - 1); base < n; base += kChunk) {
-        match256(keys, base, lane, j, n, key, m);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            unsigned long long mq = m[q];
-            while (mq) {
-                int64_t mine = -1;  // this lane group's occurrence of the next G matches
-#pragma unroll
-                for (int t = 0; t < G; ++t)
-                    if (mq) {
-                        const int bit = __ffsll(mq) - 1;
-                        mq &= mq - 1;
-                        if (t == g) mine = base + 4 * bit + q;
-                    }
-                if (mine < 0) continue;
-                if (user) {
-                    acc = add4(acc, ld4(occU + mine * D + c));
-                } else {
-                    const int64_t b = mine < B ? mine : mine - B;
-                    const float sgn = mine < B ? 1.f : -1.f;
-                    acc = fma4(sgn * coef[b], ld4(a.E + (int64_t)ku[b] * D + c), acc);
-                    acc = add4(acc, sp);
-                }
-            }
+    for_each_match<D>(keys, j, n, key, lane, [&](int64_t mine) {
+        if (user) {
+            acc = add4(acc, ld4(occU + mine * D + c));
+        } else {
+            const int64_t b = mine < B ? mine : mine - B;
+            const float sgn = mine < B ? 1.f : -1.f;
+            acc = fma4(sgn * coef[b], ld4(a.E + (int64_t)ku[b] * D + c), acc);
+            acc = add4(acc, sp);
         }
-    }
-#pragma unroll
-    for (int o = kWave / 2; o >= L; o >>= 1) {  // the G partial rows, a fixed tree
-        acc.x += __shfl_xor(acc.x, o, kWave);
-        acc.y += __shfl_xor(acc.y, o, kWave);
-        acc.z += __shfl_xor(acc.z, o, kWave);
-        acc.w += __shfl_xor(acc.w, o, kWave);
-    }
+    });
+    tree_rows<L>(acc);
     const float hg = group_sum<L>(dot4(hn, acc));  // every lane group holds the same sum now
     if (g != 0) return;
     if (user) {
@@ -239,41 +171,15 @@ __global__ __launch_bounds__(256) void sum_rows(Args a, const float* __restrict_
     }
 }
 
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Ws {
-    float *part, *occU, *coef;
-    int32_t *ku, *ki;
-    size_t total;
-};
-inline Ws carve(void* ws, int64_t B, int d) {
-    Ws w;
-    char* p = static_cast<char*>(ws);
-    size_t o = 0;
-    auto take = [&](size_t n) {
-        char* q = p ? p + o : nullptr;
-        o += al(n);
-        return q;
-    };
-    const int rpb = 256 / (d / 4);
-    w.part = reinterpret_cast<float*>(take((size_t)((B + rpb - 1) / rpb) * 2 * sizeof(float)));
-    w.occU = reinterpret_cast<float*>(take((size_t)B * d * sizeof(float)));
-    w.coef = reinterpret_cast<float*>(take((size_t)B * sizeof(float)));
-    w.ku = reinterpret_cast<int32_t*>(take((size_t)B * sizeof(int32_t)));
-    w.ki = reinterpret_cast<int32_t*>(take((size_t)2 * B * sizeof(int32_t)));
-    w.total = o;
-    return w;
-}
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline TripletWs carve(void* ws, int64_t B, int d) { return carve_triplet(ws, B, d, kPartStride, kCoef); }
 
 inline int check(const rsx_lattice_args* a, void* ws, size_t ws_bytes, Args& k) {
-    if (!a || a->batch < 1 || a->n_users < 1 || a->n_items < 1) return RSX_ERR_ARG;
-    if (a->d != 64 && a->d != 128) return RSX_ERR_UNSUPPORTED;
-    if (!a->E || !a->H || !a->triplets || !ws || !(a->batch_size > 0.f)) return RSX_ERR_ARG;
-    if (!aligned16(a->E) || !aligned16(a->H) || !aligned16(ws)) return RSX_ERR_ARG;
-    if (a->batch > kMaxBatch || a->n_users > 0x7fffffffll || a->n_items > 0x7fffffffll) return RSX_ERR_UNSUPPORTED;
-    if (ws_bytes < rsx_lattice_ws_bytes(a->batch, a->d)) return RSX_ERR_WORKSPACE;
+    if (!a) return RSX_ERR_ARG;
+    const bool own_ok = a->E && a->H && a->triplets && ws && a->batch_size > 0.f && aligned16(a->E) &&
+                        aligned16(a->H) && aligned16(ws);
+    const int rc = check_triplet(a->batch, a->n_users, a->n_items, a->d, own_ok, ws_bytes,
+                                 rsx_lattice_ws_bytes(a->batch, a->d));
+    if (rc) return rc;
     k.E = a->E, k.H = a->H, k.trip = a->triplets;
     k.nu = a->n_users, k.ni = a->n_items, k.B = a->batch, k.reg = a->reg, k.bs = a->batch_size;
     return RSX_OK;
@@ -281,8 +187,8 @@ inline int check(const rsx_lattice_args* a, void* ws, size_t ws_bytes, Args& k) 
 
 template <int D>
 int fwd(const Args& k, float* out, void* ws, hipStream_t s) {
-    constexpr int RPB = 256 / (D / 4);
-    const Ws w = carve(ws, k.B, D);
+    constexpr int RPB = RowGeom<D>::RPB;
+    const TripletWs w = carve(ws, k.B, D);
     const int nblk = (int)((k.B + RPB - 1) / RPB);
     hipLaunchKernelGGL(loss_rows<D>, dim3(nblk), dim3(256), 0, s, k, w.part);
     hipLaunchKernelGGL(finish, dim3(1), dim3(64), 0, s, (const float*)w.part, nblk, k.B, k.reg, k.bs, out);
@@ -291,8 +197,8 @@ int fwd(const Args& k, float* out, void* ws, hipStream_t s) {
 
 template <int D>
 int bwd(const Args& k, const float* go, float* gE, float* gH, void* ws, hipStream_t s) {
-    constexpr int RPB = 256 / (D / 4);
-    const Ws w = carve(ws, k.B, D);
+    constexpr int RPB = RowGeom<D>::RPB;
+    const TripletWs w = carve(ws, k.B, D);
     hipError_t e;
     if ((e = hipMemsetAsync(gE, 0, (size_t)(k.nu + k.ni) * D * sizeof(float), s)) != hipSuccess) return hip_rc(e);
     if ((e = hipMemsetAsync(gH, 0, (size_t)k.ni * D * sizeof(float), s)) != hipSuccess) return hip_rc(e);
@@ -596,17 +502,11 @@ struct BwdWs {
 };
 inline BwdWs carve_bwd(void* ws, int64_t n, int K) {
     BwdWs w;
-    char* p = static_cast<char*>(ws);
-    size_t o = 0;
-    auto take = [&](size_t b) {
-        char* q = p ? p + o : nullptr;
-        o += al(b);
-        return q;
-    };
-    w.P = reinterpret_cast<float*>(take((size_t)n * K * sizeof(float)));
-    w.gr = reinterpret_cast<float*>(take((size_t)n * sizeof(float)));
-    w.pw = reinterpret_cast<double*>(take((size_t)n * 2 * sizeof(double)));
-    w.total = o;
+    Carver cv(ws);
+    w.P = cv.take<float>((size_t)n * K * sizeof(float));
+    w.gr = cv.take<float>((size_t)n * sizeof(float));
+    w.pw = cv.take<double>((size_t)n * 2 * sizeof(double));
+    w.total = cv.total();
     return w;
 }
 
@@ -616,8 +516,7 @@ inline BwdWs carve_bwd(void* ws, int64_t n, int K) {
 using namespace rsx;
 
 extern "C" size_t rsx_lattice_ws_bytes(int64_t batch, int32_t d) {
-    if (batch < 1 || batch > lattice::kMaxBatch || (d != 64 && d != 128)) return 0;
-    return lattice::carve(nullptr, batch, d).total;
+    return triplet_ws_bytes(batch, d, lattice::kPartStride, lattice::kCoef);
 }
 
 extern "C" int rsx_lattice_loss_fwd(const rsx_lattice_args* a, float* out, void* ws, size_t ws_bytes,
@@ -635,7 +534,7 @@ extern "C" int rsx_lattice_loss_bwd(const rsx_lattice_args* a, const float* go, 
     lattice::Args k;
     const int rc = lattice::check(a, ws, ws_bytes, k);
     if (rc) return rc;
-    if (!go || !gE || !gH || !lattice::aligned16(gE) || !lattice::aligned16(gH)) return RSX_ERR_ARG;
+    if (!go || !gE || !gH || !aligned16(gE) || !aligned16(gH)) return RSX_ERR_ARG;
     hipStream_t s = as_stream(stream);
     return a->d == 64 ? lattice::bwd<64>(k, go, gE, gH, ws, s) : lattice::bwd<128>(k, go, gE, gH, ws, s);
 }
@@ -654,7 +553,7 @@ extern "C" int rsx_lattice_prop(const rsx_lattice_graph_args* a, const float* x,
     const int rc = lattice::to_graph(a, g, transpose != 0);
     if (rc) return rc;
     if (d != 64 && d != 128) return RSX_ERR_UNSUPPORTED;
-    if (!x || !y || x == y || !lattice::aligned16(x) || !lattice::aligned16(y)) return RSX_ERR_ARG;
+    if (!x || !y || x == y || !aligned16(x) || !aligned16(y)) return RSX_ERR_ARG;
     hipStream_t s = as_stream(stream);
     return d == 64 ? lattice::run_prop<64>(g, x, y, transpose != 0, s)
                    : lattice::run_prop<128>(g, x, y, transpose != 0, s);
@@ -674,14 +573,14 @@ extern "C" int rsx_lattice_graph_bwd(const rsx_lattice_graph_args* a, int32_t n_
     if (d != 64 && d != 128) return RSX_ERR_UNSUPPORTED;
     if (n_layers < 1 || n_layers > lattice::kMaxLayers) return RSX_ERR_UNSUPPORTED;
     if (!G || !X || !gF0 || (g.M == 2 && (!gF1 || !g_modal_weight)) || !ws) return RSX_ERR_ARG;
-    if (!lattice::aligned16(gF0) || !lattice::aligned16(gF1) || !lattice::aligned16(ws)) return RSX_ERR_ARG;
+    if (!aligned16(gF0) || !aligned16(gF1) || !aligned16(ws)) return RSX_ERR_ARG;
     if (ws_bytes < rsx_lattice_graph_bwd_ws_bytes(g.n, g.k, g.M)) return RSX_ERR_WORKSPACE;
     lattice::Layers ly;
     ly.n = n_layers;
     for (int l = 0; l < lattice::kMaxLayers; ++l) {
         ly.G[l] = l < n_layers ? G[l] : nullptr;
         ly.X[l] = l < n_layers ? X[l] : nullptr;
-        if (l < n_layers && (!ly.G[l] || !ly.X[l] || !lattice::aligned16(ly.G[l]) || !lattice::aligned16(ly.X[l])))
+        if (l < n_layers && (!ly.G[l] || !ly.X[l] || !aligned16(ly.G[l]) || !aligned16(ly.X[l])))
             return RSX_ERR_ARG;
     }
     const lattice::BwdWs w = lattice::carve_bwd(ws, g.n, g.K);

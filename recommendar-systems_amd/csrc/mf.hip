@@ -351,8 +351,6 @@ __global__ __launch_bounds__(256) void mf_adam(AdamJob j) {
 // --------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------
-static size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct MfWs {
     size_t coef, part, proj, gproj, wg, total;
 };

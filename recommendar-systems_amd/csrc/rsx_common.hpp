@@ -58,6 +58,24 @@ inline int device_cus() {
     return n;
 }
 
+inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// Consecutive 256-byte aligned pieces of one workspace.  With a null base every piece is
+// null and total() is the size the layout needs.
+struct Carver {
+    char* base;
+    size_t off = 0;
+    explicit Carver(void* ws) : base(static_cast<char*>(ws)) {}
+    template <class T>
+    T* take(size_t bytes) {
+        void* q = base ? base + off : nullptr;
+        off += al256(bytes);
+        return static_cast<T*>(q);
+    }
+    size_t total() const { return off; }
+};
+
 // A tuning knob read from the environment: unset -> dflt; an integer in [lo, hi] -> that
 // value; anything else (not an integer, out of range) aborts with the knob's name.
 // Knobs only re-plan launches (grid sizes, splits, phases); none changes a result.

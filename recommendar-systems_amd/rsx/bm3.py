@@ -175,14 +175,7 @@ class BM3(GeneralRecommender):
 
     @staticmethod
     def check_config(config):
-        import torch.distributed as dist
-
-        if not config.get("use_gpu", True):
-            raise unsupported("use_gpu: False")
-        if torch.device(config["device"]).type != "cuda":
-            raise unsupported("no ROCm GPU for this process")
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise unsupported(f"torch.distributed world size {dist.get_world_size()} > 1")
+        ops.require_single_gpu(config, unsupported)
         if config["embedding_size"] not in SUPPORTED_D:
             raise unsupported(f"embedding_size {config['embedding_size']} not in {SUPPORTED_D}")
 

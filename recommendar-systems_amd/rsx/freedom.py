@@ -35,7 +35,8 @@ from . import graph, ops
 from .bm3 import _Project
 from .layergcn import DeviceEdgeDropout
 from .recommender import GeneralRecommender
-from .smore import _DevGraph, _ego, _PropMean, _PropMeanRows, _RowTags, knn_graph_device, load_reference_knn
+from .smore import (_DevGraph, _ego, _join_tables, _PropMean, _PropMeanRows, _RowsOff, _RowTags, knn_graph_device,
+                    load_reference_knn)
 
 SUPPORTED_D = (64, 128)
 
@@ -181,14 +182,7 @@ class FREEDOM(GeneralRecommender):
 
     @staticmethod
     def check_config(config):
-        import torch.distributed as dist
-
-        if not config.get("use_gpu", True):
-            raise unsupported("use_gpu: False")
-        if torch.device(config["device"]).type != "cuda":
-            raise unsupported("no ROCm GPU for this process")
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise unsupported(f"torch.distributed world size {dist.get_world_size()} > 1")
+        ops.require_single_gpu(config, unsupported)
         d = config["embedding_size"]
         if d not in SUPPORTED_D:
             raise unsupported(f"embedding_size {d} not in {SUPPORTED_D}")
@@ -254,13 +248,7 @@ class FREEDOM(GeneralRecommender):
         self.item_id_embedding = nn.Embedding(ni, d)
         nn.init.xavier_uniform_(self.user_embedding.weight)
         nn.init.xavier_uniform_(self.item_id_embedding.weight)
-        # the two tables as adjacent row blocks of one device buffer: the UI backbone's ego
-        # table [U; I] is that buffer itself (rsx.smore._ego)
-        joint = torch.empty(nu + ni, d, dtype=torch.float32, device=self.device)
-        joint[:nu].copy_(self.user_embedding.weight.detach())
-        joint[nu:].copy_(self.item_id_embedding.weight.detach())
-        self.user_embedding.weight = nn.Parameter(joint[:nu])
-        self.item_id_embedding.weight = nn.Parameter(joint[nu:])
+        _join_tables(self.user_embedding, self.item_id_embedding, self.device)
         if self.v_feat is not None:
             self.image_embedding = nn.Embedding.from_pretrained(self.v_feat.clone(), freeze=False)
             self.image_trs = nn.Linear(self.v_feat.shape[1], self.feat_embed_dim)
@@ -279,7 +267,7 @@ class FREEDOM(GeneralRecommender):
             mm = freedom_item_graph(self.v_feat, self.t_feat, self.knn_k, self.mm_image_weight, self.knn_mode)
         self.mm_adj = _DevGraph(*mm, ni, ni, self.device, kchunk)
         self._ws = workspace(max(int(config["train_batch_size"] or 1), 1), d, self.device)
-        self._rows_off = {}
+        self._rows_off = _RowsOff(self.n_users, self.device)
         self._tags = None
         self._eval_cache = None
         self.last_terms = None  # the loss's four words of the last calculate_loss (device)
@@ -340,13 +328,8 @@ class FREEDOM(GeneralRecommender):
         d = self.embedding_dim
         if L.lib().rsx_freedom_ws_bytes(B, d) > self._ws.numel():  # a batch above the config's
             self._ws = workspace(B, d, self.device)
-        off = self._rows_off.get(B)
-        if off is None:
-            off = self._rows_off[B] = torch.cat([torch.zeros(B, dtype=torch.int64, device=self.device),
-                                                 torch.full((2 * B,), self.n_users, dtype=torch.int64,
-                                                            device=self.device)])
         trip = interaction[:3].contiguous()
-        rows = trip.reshape(-1) + off  # [users; nu + positives; nu + negatives]
+        rows = self._rows_off.rows(trip)
         ego = _ego(self.user_embedding.weight, self.item_id_embedding.weight)
         if 1 <= self.n_ui_layers <= 4:
             if self._tags is None:

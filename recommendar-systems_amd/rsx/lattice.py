@@ -42,7 +42,7 @@ from . import _lib as L
 from . import graph, ops
 from .bm3 import _Project
 from .recommender import GeneralRecommender
-from .smore import _ego, _PropMean, _PropMeanRows, _RowTags
+from .smore import _ego, _join_tables, _PropMean, _PropMeanRows, _RowsOff, _RowTags
 
 SUPPORTED_D = (64, 128)
 MAX_ITEM_LAYERS = 4
@@ -258,14 +258,7 @@ class LATTICE(GeneralRecommender):
 
     @staticmethod
     def check_config(config):
-        import torch.distributed as dist
-
-        if not config.get("use_gpu", True):
-            raise unsupported("use_gpu: False")
-        if torch.device(config["device"]).type != "cuda":
-            raise unsupported("no ROCm GPU for this process")
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise unsupported(f"torch.distributed world size {dist.get_world_size()} > 1")
+        ops.require_single_gpu(config, unsupported)
         if config["cf_model"] not in ("lightgcn", "mf"):
             raise unsupported(f"cf_model {config['cf_model']!r} (lightgcn and mf are built)")
         d = config["embedding_size"]
@@ -317,13 +310,7 @@ class LATTICE(GeneralRecommender):
         self.item_id_embedding = nn.Embedding(ni, d)
         nn.init.xavier_uniform_(self.user_embedding.weight)
         nn.init.xavier_uniform_(self.item_id_embedding.weight)
-        # the two tables as adjacent row blocks of one device buffer: the backbone's ego table
-        # [U; I] is that buffer itself (rsx.smore._ego)
-        joint = torch.empty(nu + ni, d, dtype=torch.float32, device=self.device)
-        joint[:nu].copy_(self.user_embedding.weight.detach())
-        joint[nu:].copy_(self.item_id_embedding.weight.detach())
-        self.user_embedding.weight = nn.Parameter(joint[:nu])
-        self.item_id_embedding.weight = nn.Parameter(joint[nu:])
+        _join_tables(self.user_embedding, self.item_id_embedding, self.device)
         # the original graphs: always from the features (no dense cache is read or written)
         self._orig = {}
         if self.v_feat is not None:
@@ -341,7 +328,7 @@ class LATTICE(GeneralRecommender):
         self.mods = [m for m in ("image", "text") if m in self._orig]
         self.item_graph = None  # the ItemGraph of the last training build
         self._ws = workspace(max(int(config["train_batch_size"] or 1), 1), d, self.device)
-        self._rows_off = {}
+        self._rows_off = _RowsOff(self.n_users, self.device)
         self._tags = None
         self._eval_cache = None
         self.last_terms = None  # the loss's three words of the last calculate_loss (device)
@@ -405,13 +392,8 @@ class LATTICE(GeneralRecommender):
         d = self.embedding_dim
         if L.lib().rsx_lattice_ws_bytes(B, d) > self._ws.numel():  # a batch above the config's
             self._ws = workspace(B, d, self.device)
-        off = self._rows_off.get(B)
-        if off is None:
-            off = self._rows_off[B] = torch.cat([torch.zeros(B, dtype=torch.int64, device=self.device),
-                                                 torch.full((2 * B,), self.n_users, dtype=torch.int64,
-                                                            device=self.device)])
         trip = interaction[:3].contiguous()
-        rows = trip.reshape(-1) + off  # [users; nu + positives; nu + negatives]
+        rows = self._rows_off.rows(trip)
         E = self._backbone(rows)
         build, self.build_item_graph = self.build_item_graph or self.item_graph is None, False
         H = self._item_table(build)

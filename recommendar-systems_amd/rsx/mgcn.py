@@ -34,7 +34,7 @@ from .bm3 import _Project
 from .lightgcn import _BprLoss
 from .nn import RsxLinear
 from .recommender import GeneralRecommender
-from .smore import SMORE, _DevGraph, _ego, _PropMean, _PropMeanRows, _RowTags
+from .smore import SMORE, _DevGraph, _ego, _join_tables, _PropMean, _PropMeanRows, _RowsOff, _RowTags
 
 CL_TEMPERATURE = 0.2  # mgcn.py:250-251
 
@@ -51,14 +51,7 @@ class MGCN(GeneralRecommender):
 
     @staticmethod
     def check_config(config):
-        import torch.distributed as dist
-
-        if not config.get("use_gpu", True):
-            raise unsupported("use_gpu: False")
-        if torch.device(config["device"]).type != "cuda":
-            raise unsupported("no ROCm GPU for this process")
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            raise unsupported(f"torch.distributed world size {dist.get_world_size()} > 1")
+        ops.require_single_gpu(config, unsupported)
         if not MF.supported(config["embedding_size"]):
             raise unsupported(f"embedding_size {config['embedding_size']} not in (64, 128)")
         if int(config["knn_k"]) > 32:
@@ -90,13 +83,7 @@ class MGCN(GeneralRecommender):
         self.item_id_embedding = nn.Embedding(ni, d)
         nn.init.xavier_uniform_(self.user_embedding.weight)
         nn.init.xavier_uniform_(self.item_id_embedding.weight)
-        # the two tables as adjacent row blocks of one device buffer: the UI backbone's ego
-        # table [U; I] is that buffer itself (rsx.smore._ego)
-        joint = torch.empty(nu + ni, d, dtype=torch.float32, device=self.device)
-        joint[:nu].copy_(self.user_embedding.weight.detach())
-        joint[nu:].copy_(self.item_id_embedding.weight.detach())
-        self.user_embedding.weight = nn.Parameter(joint[:nu])
-        self.item_id_embedding.weight = nn.Parameter(joint[nu:])
+        _join_tables(self.user_embedding, self.item_id_embedding, self.device)
         # norm_adj and R (mgcn.py:45-47,109-136: SMORE's normalisation)
         drp, dcol, dval = ops.adj_build(im.row.astype(np.int64), im.col.astype(np.int64), nu, ni, ops.ADJ_SMORE,
                                         self.device)
@@ -129,7 +116,7 @@ class MGCN(GeneralRecommender):
         flag = config.get("rsx_mgcn_batch_rows", True)
         self.batch_rows = bool(flag if flag is not None else True)
         self._bidx = {}
-        self._rows_off = {}
+        self._rows_off = _RowsOff(self.n_users, self.device)
         self._tags = None
         self._eval_cache = None
         self.to(self.device)
@@ -177,8 +164,6 @@ class MGCN(GeneralRecommender):
         if c is None:
             ar = torch.arange(B, dtype=torch.int64, device=self.device)
             c = self._bidx[B] = (ar, torch.stack([ar, ar, ar + B]).contiguous())
-            self._rows_off[B] = torch.cat([torch.zeros(B, dtype=torch.int64, device=self.device),
-                                           torch.full((2 * B,), self.n_users, dtype=torch.int64, device=self.device)])
         return c
 
     def calculate_loss(self, interaction):
@@ -187,7 +172,7 @@ class MGCN(GeneralRecommender):
             # the fuser is row-local and the loss reads all / side / content at the batch's
             # users, positives and negatives alone: its other rows are never computed
             ar, trip = self._batch_index(B)
-            rows = interaction[:3].reshape(-1) + self._rows_off[B]  # [users; nu + positives; nu + negatives]
+            rows = self._rows_off.rows(interaction[:3])
             content, image_embeds, text_embeds = self._views(rows)
             all_c, side_c, content_c = MF.fuse_rows(self, content, image_embeds, text_embeds, rows)
             total, _ = SF.smore_loss_rows(all_c, side_c, content_c, trip, ar, B, self.reg_weight, self.batch_size,

@@ -42,6 +42,19 @@ def require_device(device) -> torch.device:
     return device
 
 
+def require_single_gpu(config, unsupported) -> None:
+    """The start of a one-GPU model's check_config: a CPU configuration, a process without a
+    GPU and more than one rank are refused with the model's own `unsupported(what)` error."""
+    import torch.distributed as dist
+
+    if not config.get("use_gpu", True):
+        raise unsupported("use_gpu: False")
+    if torch.device(config["device"]).type != "cuda":
+        raise unsupported("no ROCm GPU for this process")
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise unsupported(f"torch.distributed world size {dist.get_world_size()} > 1")
+
+
 # ---------------------------------------------------------------------------
 # CSR adjacency + schedule
 # ---------------------------------------------------------------------------

@@ -110,6 +110,37 @@ def _ego(u: torch.Tensor, i: torch.Tensor) -> torch.Tensor:
     return _Joined.apply(u, i) if adjacent else torch.cat([u, i], dim=0)
 
 
+def _join_tables(user_embedding: nn.Embedding, item_embedding: nn.Embedding, device) -> None:
+    """Moves the two tables (created and initialised by the caller, on the CPU generator as the
+    reference does) into adjacent row blocks of one device buffer: the UI backbone's ego table
+    [U; I] is then that buffer itself (_ego), no per-forward concatenation copy."""
+    u, i = user_embedding.weight.detach(), item_embedding.weight.detach()
+    nu = u.shape[0]
+    joint = torch.empty(nu + i.shape[0], u.shape[1], dtype=torch.float32, device=device)
+    joint[:nu].copy_(u)
+    joint[nu:].copy_(i)
+    user_embedding.weight = nn.Parameter(joint[:nu])
+    item_embedding.weight = nn.Parameter(joint[nu:])
+
+
+class _RowsOff(dict):
+    """off[B] = [0] * B ++ [n_users] * 2 B (int64, on the device), made once per batch length
+    and kept: a captured graph step must not allocate.  rows(trip) are the batch's rows of
+    [U; I] for int64 triplets [3, B]: [users; nu + positives; nu + negatives]."""
+
+    def __init__(self, n_users: int, device):
+        super().__init__()
+        self.n_users, self.device = int(n_users), device
+
+    def __missing__(self, B: int) -> torch.Tensor:
+        off = self[B] = torch.cat([torch.zeros(B, dtype=torch.int64, device=self.device),
+                                   torch.full((2 * B,), self.n_users, dtype=torch.int64, device=self.device)])
+        return off
+
+    def rows(self, trip: torch.Tensor) -> torch.Tensor:
+        return trip.reshape(-1) + self[trip.shape[1]]
+
+
 class _RowTags:
     """Batch-row tags for the tagged propagation: row r is in the batch when
     row_tag[r] == *tag_dev; `mark` bumps the device tag and tags the batch's rows
@@ -345,14 +376,7 @@ class SMORE(GeneralRecommender):
         nn.init.xavier_uniform_(self.item_id_embedding.weight)
         nu, ni = self.n_users, self.n_items
         if torch.device(self.device).type == "cuda":
-            # the two tables as adjacent row blocks of one device buffer (drawn on the CPU as
-            # the reference does, then copied): the UI backbone's ego table [U; I] is that
-            # buffer itself (_ego), no per-forward concatenation copy
-            joint = torch.empty(nu + ni, d, dtype=torch.float32, device=self.device)
-            joint[:nu].copy_(self.user_embedding.weight.detach())
-            joint[nu:].copy_(self.item_id_embedding.weight.detach())
-            self.user_embedding.weight = nn.Parameter(joint[:nu])
-            self.item_id_embedding.weight = nn.Parameter(joint[nu:])
+            _join_tables(self.user_embedding, self.item_id_embedding, self.device)
         im = self.interaction_matrix
         if os.environ.get("RSX_GRAPH_BUILDER", "device") == "host":
             rp, col, val = graph.smore_norm_adj(im.row.astype(np.int64), im.col.astype(np.int64), nu, ni)
@@ -417,7 +441,7 @@ class SMORE(GeneralRecommender):
         # training loss on the batch rows only (rsx_smore_batch_rows: False = full tables)
         self.batch_rows = bool(config.get("rsx_smore_batch_rows", True))
         self._bidx = {}
-        self._rows_off = {}
+        self._rows_off = _RowsOff(self.n_users, self.device)
         self._tags = None
         self._vtags = None  # the views' backward batch-row tags (rsx.smore_fuse._ViewProp3)
         self.batch_views = bool(config.get("rsx_smore_batch_views", True))
@@ -768,8 +792,6 @@ class SMORE(GeneralRecommender):
         if c is None:
             ar = torch.arange(B, dtype=torch.int64, device=self.device)
             c = self._bidx[B] = (ar, torch.stack([ar, ar, ar + B]).contiguous())
-            self._rows_off[B] = torch.cat([torch.zeros(B, dtype=torch.int64, device=self.device),
-                                           torch.full((2 * B,), self.n_users, dtype=torch.int64, device=self.device)])
         return c
 
     def _calculate_loss_rows(self, interaction):
@@ -780,7 +802,7 @@ class SMORE(GeneralRecommender):
         form (duplicate rows are computed once per occurrence, their gradients added)."""
         nu, B = self.n_users, interaction.shape[1]
         ar, trip = self._batch_index(B)
-        rows = interaction[:3].reshape(-1) + self._rows_off[B]  # [users; nu + positives; nu + negatives]
+        rows = self._rows_off.rows(interaction[:3])
         exch = self._exch  # data-parallel SMORE: the batch-row gradient exchange
         content, image_embeds, text_embeds, fusion_embeds, seed = self._views_fused(
             train=True, rows=rows, bw_rows=exch.union if exch is not None else None)

@@ -101,7 +101,7 @@ def _run_loss(x, nu, reg, H, T, V, cuda):
 
 
 @pytest.mark.parametrize("nu,ni", [(5, 7), (400, 200)])
-@pytest.mark.parametrize("B", [1, 67, 512])
+@pytest.mark.parametrize("B", [1, 67, 300, 512])
 @pytest.mark.parametrize("d", [64, 128])
 def test_loss_kernel_vs_restatement(cuda, d, B, nu, ni):
     x = _inputs(d, B, nu, ni, 100 + d + B + nu)
