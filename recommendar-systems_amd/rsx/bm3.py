@@ -6,7 +6,7 @@ reg_weight, cl_weight, dropout), parameter names, creation order and initial dra
 without negatives (`use_neg_sampling: False`: the loader yields [2, B] pairs) against a
 dropped-out, gradient-stopped copy of its own embeddings:
 
-* the mean-of-layers propagation of [U; I] and its backward: `rsx.smore._PropMean` (the
+* the mean-of-layers propagation of [U; I] and its backward: `rsx.blocks._PropMean` (the
   dense variant: the regulariser's gradient touches every row), the two tables adjacent in
   one buffer so that the ego table is that buffer (`_ego`);
 * the text / image projections over the whole feature tables: `rsx_linear_rows_fwd`
@@ -31,8 +31,8 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from .blocks import _ego, _join_tables, _Project, _PropMean
 from .recommender import GeneralRecommender
-from .smore import _ego, _PropMean
 
 SUPPORTED_D = (32, 64, 128)
 STREAMS = ("user", "item", "text", "image")
@@ -116,10 +116,7 @@ def loss_bwd(args: "L.Bm3Args", go: torch.Tensor, E, T, V, P):
 
 
 def workspace(batch: int, d: int, device) -> torch.Tensor:
-    n = L.lib().rsx_bm3_ws_bytes(int(batch), int(d))
-    if n == 0:
-        raise unsupported(f"batch {batch}, embedding_size {d}")
-    return torch.empty(n, dtype=torch.uint8, device=device)
+    return ops.loss_workspace(L.lib().rsx_bm3_ws_bytes, batch, d, device, unsupported)
 
 
 class _Bm3Loss(torch.autograd.Function):
@@ -150,23 +147,6 @@ class _Bm3Loss(torch.autograd.Function):
         return None, None, None, gE, gE[ctx.n_users:], gP, gpb, gT, gV
 
 
-class _Project(torch.autograd.Function):
-    """x W^T + b over every row of a feature table: rsx_linear_rows_fwd, and rsx_linear_bwd
-    (dX, dW, db in one pass over the rows) for the dense gradient BM3 sends back."""
-
-    @staticmethod
-    def forward(ctx, x, W, b):
-        x, W, b = x.contiguous(), W.contiguous(), b.contiguous()
-        ctx.save_for_backward(x, W)
-        return ops.linear_rows_fwd(x, W, b, None)
-
-    @staticmethod
-    def backward(ctx, g):
-        x, W = ctx.saved_tensors
-        dw, dx, db = ops.linear_bwd(g.contiguous(), x, W, bias=True)
-        return dx, dw, db
-
-
 class BM3(GeneralRecommender):
     # calculate_loss has no host syncs and no data-dependent host branches: the Trainer may
     # capture a batch in a HIP graph (rsx.trainer._GraphStep); no per-epoch buffer rebuilds
@@ -190,9 +170,7 @@ class BM3(GeneralRecommender):
         self.dropout = float(config["dropout"])
         if not 0.0 <= self.dropout < 1.0:
             raise unsupported(f"dropout {self.dropout} outside [0, 1)")
-        for name, f in (("vision", self.v_feat), ("text", self.t_feat)):
-            if f is not None and f.shape[1] % 4:
-                raise unsupported(f"{name} feature width {f.shape[1]} is not a multiple of 4")
+        self.require_features(unsupported, need=0, vision="vision")
         self.n_nodes = nu_ni = self.n_users + self.n_items
         nu, ni = self.n_users, self.n_items
         # parameters in the reference's creation order (identical init under init_seed), drawn
@@ -201,12 +179,10 @@ class BM3(GeneralRecommender):
                         None if self.t_feat is None else int(self.t_feat.shape[1]))
         dev = self.device
         # the two tables as adjacent row blocks of one device buffer: the propagation's ego
-        # table [U; I] is that buffer itself (rsx.smore._ego), no per-forward concatenation
-        joint = torch.empty(nu_ni, d, dtype=torch.float32, device=dev)
-        joint[:nu].copy_(init["user_embedding.weight"])
-        joint[nu:].copy_(init["item_id_embedding.weight"])
-        self.user_embedding = nn.Embedding(nu, d, _weight=joint[:nu])
-        self.item_id_embedding = nn.Embedding(ni, d, _weight=joint[nu:])
+        # table [U; I] is that buffer itself (rsx.blocks._ego), no per-forward concatenation
+        self.user_embedding = nn.Embedding(nu, d, _weight=init["user_embedding.weight"])
+        self.item_id_embedding = nn.Embedding(ni, d, _weight=init["item_id_embedding.weight"])
+        _join_tables(self.user_embedding, self.item_id_embedding, dev)
         self.predictor = nn.Linear(d, d)
         for name, f in (("image", self.v_feat), ("text", self.t_feat)):
             if f is not None:
@@ -250,8 +226,7 @@ class BM3(GeneralRecommender):
         ignored).  keep_masks: optional dict stream -> packed keep mask (rsx_bm3_args) in
         place of the hashed dropout."""
         users, items = interaction[0], interaction[1]
-        if L.lib().rsx_bm3_ws_bytes(users.numel(), self.embedding_dim) > self._ws.numel():  # a batch above the config's
-            self._ws = workspace(users.numel(), self.embedding_dim, self.device)
+        self._ws = ops.grow_workspace(L.lib().rsx_bm3_ws_bytes, self._ws, users.numel(), self.embedding_dim)
         if self.dropout > 0.0 and keep_masks is None:
             self._drop_seed.add_(1)
         E, H, T, V = self._tables()

@@ -12,8 +12,8 @@ weights), forward, loss and scoring (:166-222):
 * the frozen item graph mm_adj (:64-100): binary top-k graphs per modality, degree
   normalised, mixed by mm_image_weight (`freedom_item_graph`: construction-time host work;
   the neighbour ids from rsx_knn_graph or a CPU top-k);
-* the UI backbone on the batch rows (`_PropMeanRows`), the item graph's propagation
-  (`_DevGraph`), the whole-table feature projections (`rsx.bm3._Project`);
+* the UI backbone on the batch rows (`rsx.blocks.ui_backbone`), the item graph's propagation
+  (`_DevGraph`), the whole-table feature projections (`rsx.blocks._Project`);
 * the three-term BPR loss, forward and backward: rsx_freedom_loss_fwd / _bwd
   (csrc/freedom.hip), deterministic;
 * evaluation: the fused full-sort on the cached eval-mode tables.
@@ -32,11 +32,10 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import graph, ops
-from .bm3 import _Project
+from .blocks import (_DevGraph, _ego, _join_tables, _Project, _PropMean, _RowsOff, knn_graph_device,
+                     load_reference_knn, ui_backbone)
 from .layergcn import DeviceEdgeDropout
-from .recommender import GeneralRecommender
-from .smore import (_DevGraph, _ego, _join_tables, _PropMean, _PropMeanRows, _RowsOff, _RowTags, knn_graph_device,
-                    load_reference_knn)
+from .recommender import EvalTables, GeneralRecommender
 
 SUPPORTED_D = (64, 128)
 
@@ -49,10 +48,7 @@ def unsupported(what: str) -> RuntimeError:
 # the fused loss
 # ---------------------------------------------------------------------------
 def workspace(batch: int, d: int, device) -> torch.Tensor:
-    n = L.lib().rsx_freedom_ws_bytes(int(batch), int(d))
-    if n == 0:
-        raise unsupported(f"batch {batch}, embedding_size {d}")
-    return torch.empty(n, dtype=torch.uint8, device=device)
+    return ops.loss_workspace(L.lib().rsx_freedom_ws_bytes, batch, d, device, unsupported)
 
 
 def freedom_args(E, H, T, V, triplets, n_users: int, reg: float) -> "L.FreedomArgs":
@@ -173,7 +169,7 @@ def freedom_item_graph(v_feat, t_feat, k: int, image_weight: float, mode: str = 
 # ---------------------------------------------------------------------------
 # the model
 # ---------------------------------------------------------------------------
-class FREEDOM(GeneralRecommender):
+class FREEDOM(EvalTables, GeneralRecommender):
     # a training batch has no host syncs: the Trainer may capture it in a HIP graph.  The
     # epoch graph's buffers change in pre_epoch_processing, so the captures are dropped at
     # every epoch start
@@ -203,11 +199,7 @@ class FREEDOM(GeneralRecommender):
         except AssertionError as e:  # recommender.py: "Features all NONE"
             raise unsupported("no feature file at all") from e
         ops.require_device(self.device)
-        if self.v_feat is None and self.t_feat is None:
-            raise unsupported("no feature file at all")
-        for name, f in (("image", self.v_feat), ("text", self.t_feat)):
-            if f is not None and f.shape[1] % 4:
-                raise unsupported(f"{name} feature width {f.shape[1]} is not a multiple of 4")
+        self.require_features(unsupported)
         self.embedding_dim = d = config["embedding_size"]
         self.feat_embed_dim = config["feat_embed_dim"]
         self.knn_k = int(config["knn_k"])
@@ -269,7 +261,6 @@ class FREEDOM(GeneralRecommender):
         self._ws = workspace(max(int(config["train_batch_size"] or 1), 1), d, self.device)
         self._rows_off = _RowsOff(self.n_users, self.device)
         self._tags = None
-        self._eval_cache = None
         self.last_terms = None  # the loss's four words of the last calculate_loss (device)
         self.to(self.device)
 
@@ -326,41 +317,14 @@ class FREEDOM(GeneralRecommender):
     def calculate_loss(self, interaction):
         B = interaction.shape[1]
         d = self.embedding_dim
-        if L.lib().rsx_freedom_ws_bytes(B, d) > self._ws.numel():  # a batch above the config's
-            self._ws = workspace(B, d, self.device)
+        self._ws = ops.grow_workspace(L.lib().rsx_freedom_ws_bytes, self._ws, B, d)
         trip = interaction[:3].contiguous()
         rows = self._rows_off.rows(trip)
         ego = _ego(self.user_embedding.weight, self.item_id_embedding.weight)
-        if 1 <= self.n_ui_layers <= 4:
-            if self._tags is None:
-                self._tags = _RowTags(self.n_nodes, self.device)
-            self._tags.mark(rows)
-            E = _PropMeanRows.apply(ego, self.train_adj, self.n_ui_layers, self._tags, rows)
-        else:
-            E = _PropMean.apply(ego, self.train_adj, self.n_ui_layers)
+        E = ui_backbone(self, ego, self.train_adj, self.n_ui_layers, rows)
         H = self._item_prop()
         T, V, bt, bv = self._projected()
         keep = {}
         loss = _FreedomLoss.apply((self.n_users, self.reg_weight, self._ws, keep), trip, E, H, T, V, bt, bv)
         self.last_terms = keep["terms"]
         return loss
-
-    # ------------------------------------------------------------ evaluation
-    def _eval_tables(self):
-        with torch.no_grad():
-            if self._eval_cache is None:
-                u, i = self.forward(self.norm_adj_csr)
-                self._eval_cache = (u.contiguous(), i.contiguous())
-        return self._eval_cache
-
-    def full_sort_predict(self, interaction):
-        u, i = self._eval_tables()
-        return ops.score_dense(u, interaction[0].contiguous(), i)
-
-    def full_sort_topk(self, interaction, k, eval_data):
-        u, i = self._eval_tables()
-        return ops.fullsort_topk(u, interaction[0].contiguous(), i, eval_data.mask_rowptr, eval_data.mask_col, k)
-
-    def train(self, mode: bool = True):
-        self._eval_cache = None
-        return super().train(mode)

@@ -8,7 +8,7 @@ weights), forward, loss and scoring (:132-237):
 
 * the UI graph (:100-122): D^-1 (A + I), row-normalised with self loops, float32 as scipy
   computes it (`graph.lattice_norm_adj`); its backward runs on a second CSR of the same
-  structure holding the transposed values (`_PropMean` / `_PropMeanRows` with a transpose
+  structure holding the transposed values (`rsx.blocks.ui_backbone` with a transpose
   operand);
 * the original graphs (:63-87): rsx_knn_graph's lists on the raw feature tables, always
   built from the features (the reference's dense caches are neither read nor written);
@@ -40,9 +40,8 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import graph, ops
-from .bm3 import _Project
-from .recommender import GeneralRecommender
-from .smore import _ego, _join_tables, _PropMean, _PropMeanRows, _RowsOff, _RowTags
+from .blocks import _ego, _join_tables, _Project, _RowsOff, ui_backbone
+from .recommender import EvalTables, GeneralRecommender
 
 SUPPORTED_D = (64, 128)
 MAX_ITEM_LAYERS = 4
@@ -56,10 +55,7 @@ def unsupported(what: str) -> RuntimeError:
 # the fused loss
 # ---------------------------------------------------------------------------
 def workspace(batch: int, d: int, device) -> torch.Tensor:
-    n = L.lib().rsx_lattice_ws_bytes(int(batch), int(d))
-    if n == 0:
-        raise unsupported(f"batch {batch}, embedding_size {d}")
-    return torch.empty(n, dtype=torch.uint8, device=device)
+    return ops.loss_workspace(L.lib().rsx_lattice_ws_bytes, batch, d, device, unsupported)
 
 
 def lattice_args(E, H, triplets, n_users: int, reg: float, batch_size: float) -> "L.LatticeArgs":
@@ -123,14 +119,7 @@ def knn_lists(feat: torch.Tensor, k: int):
     n, f = x.shape
     if k > 32 or k > n or f % 4:
         raise unsupported(f"knn_k {k} with {n} items, feature width {f}")
-    lib = L.lib()
-    v = torch.empty(n, k, dtype=torch.float32, device=x.device)
-    i = torch.empty(n, k, dtype=torch.int64, device=x.device)
-    w = torch.empty(n, k, dtype=torch.float32, device=x.device)
-    ws = torch.empty(max(int(lib.rsx_knn_ws_bytes(n, f)), 4), dtype=torch.uint8, device=x.device)
-    L.check(lib.rsx_knn_graph(ops._p(x), n, f, k, ops._p(v), ops._p(i), ops._p(w), ops._p(ws), ws.numel(),
-                              ops._stream()), "rsx_knn_graph")
-    return i, w
+    return ops.knn_lists(x, k)[1:]
 
 
 class ItemGraph:
@@ -249,7 +238,7 @@ class _ItemProp(torch.autograd.Function):
 # ---------------------------------------------------------------------------
 # the model
 # ---------------------------------------------------------------------------
-class LATTICE(GeneralRecommender):
+class LATTICE(EvalTables, GeneralRecommender):
     # a steady training batch has no host syncs: the Trainer may capture it in a HIP graph.
     # The item graph's buffers change at every build, so the captures are dropped at every
     # epoch start, and the build batch itself runs eagerly (graph_step_eager)
@@ -279,11 +268,7 @@ class LATTICE(GeneralRecommender):
         except AssertionError as e:  # recommender.py: "Features all NONE"
             raise unsupported("no feature file at all") from e
         ops.require_device(self.device)
-        if self.v_feat is None and self.t_feat is None:
-            raise unsupported("no feature file at all")
-        for name, f in (("image", self.v_feat), ("text", self.t_feat)):
-            if f is not None and f.shape[1] % 4:
-                raise unsupported(f"{name} feature width {f.shape[1]} is not a multiple of 4")
+        self.require_features(unsupported)
         self.embedding_dim = d = config["embedding_size"]
         self.feat_embed_dim = config["feat_embed_dim"]
         self.weight_size = list(config["weight_size"])
@@ -330,7 +315,6 @@ class LATTICE(GeneralRecommender):
         self._ws = workspace(max(int(config["train_batch_size"] or 1), 1), d, self.device)
         self._rows_off = _RowsOff(self.n_users, self.device)
         self._tags = None
-        self._eval_cache = None
         self.last_terms = None  # the loss's three words of the last calculate_loss (device)
         self.to(self.device)
 
@@ -362,13 +346,7 @@ class LATTICE(GeneralRecommender):
         ego = _ego(self.user_embedding.weight, self.item_id_embedding.weight)
         if self.cf_model == "mf":
             return ego
-        K = self.n_ui_layers
-        if rows is not None and 1 <= K <= 4:
-            if self._tags is None:
-                self._tags = _RowTags(self.n_nodes, self.device)
-            self._tags.mark(rows)
-            return _PropMeanRows.apply(ego, self.norm_adj_csr, K, self._tags, rows, self.norm_adj_t_csr)
-        return _PropMean.apply(ego, self.norm_adj_csr, K, self.norm_adj_t_csr)
+        return ui_backbone(self, ego, self.norm_adj_csr, self.n_ui_layers, rows, AT=self.norm_adj_t_csr)
 
     def _item_table(self, build: bool):
         h0 = self.item_id_embedding.weight
@@ -390,8 +368,7 @@ class LATTICE(GeneralRecommender):
     def calculate_loss(self, interaction):
         B = interaction.shape[1]
         d = self.embedding_dim
-        if L.lib().rsx_lattice_ws_bytes(B, d) > self._ws.numel():  # a batch above the config's
-            self._ws = workspace(B, d, self.device)
+        self._ws = ops.grow_workspace(L.lib().rsx_lattice_ws_bytes, self._ws, B, d)
         trip = interaction[:3].contiguous()
         rows = self._rows_off.rows(trip)
         E = self._backbone(rows)
@@ -405,22 +382,8 @@ class LATTICE(GeneralRecommender):
     # ------------------------------------------------------------ evaluation
     def _eval_tables(self):
         with torch.no_grad():
-            if self._eval_cache is None:
-                g = self.build_graph()
-                E = self._backbone()
-                H = _ItemProp.apply(self.item_id_embedding.weight, g, self.n_layers, False, None)
-                items = E[self.n_users:] + F.normalize(H, p=2, dim=1)
-                self._eval_cache = (E[: self.n_users].contiguous(), items.contiguous())
-        return self._eval_cache
-
-    def full_sort_predict(self, interaction):
-        u, i = self._eval_tables()
-        return ops.score_dense(u, interaction[0].contiguous(), i)
-
-    def full_sort_topk(self, interaction, k, eval_data):
-        u, i = self._eval_tables()
-        return ops.fullsort_topk(u, interaction[0].contiguous(), i, eval_data.mask_rowptr, eval_data.mask_col, k)
-
-    def train(self, mode: bool = True):
-        self._eval_cache = None
-        return super().train(mode)
+            g = self.build_graph()
+            E = self._backbone()
+            H = _ItemProp.apply(self.item_id_embedding.weight, g, self.n_layers, False, None)
+            items = E[self.n_users:] + F.normalize(H, p=2, dim=1)
+            return E[: self.n_users].contiguous(), items.contiguous()

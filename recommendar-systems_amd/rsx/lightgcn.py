@@ -49,14 +49,6 @@ from .engine import LightGCNEngine
 from .recommender import GeneralRecommender
 
 
-def _world():
-    import torch.distributed as dist
-
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_world_size(), dist.get_rank()
-    return 1, 0
-
-
 def propagate_mean(engine, x: torch.Tensor) -> torch.Tensor:
     """mean_{k=0..K} A^k x with the engine's adjacency (fresh output tensor)."""
     x = x.contiguous()
@@ -121,7 +113,7 @@ class LightGCN(GeneralRecommender):
         i0 = nn.init.xavier_uniform_(torch.empty(self.n_items, self.latent_dim))
         im = self.interaction_matrix
         wd = config["weight_decay"] or 0.0
-        world, rank = _world()
+        world, rank = ops._world()
         if self.cpu:  # torch.ops.rsx's CPU kernels; one process (the reference's CPU run)
             from .cpu_engine import CpuGCNEngine
 

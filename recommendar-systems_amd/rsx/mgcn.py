@@ -6,11 +6,11 @@ order (reference src/models/mgcn.py:22-104, so `init_seed` gives the reference's
 weights), forward, loss and scoring (:146-263):
 
 * the SMORE-normalised user-item graph (rsx_adj_build, ADJ_SMORE), its user block R and
-  the two kNN item graphs (one knn_k; rsx.smore's builders and caches);
+  the two kNN item graphs (one knn_k; rsx.blocks' builders and caches);
 * the feature projections over the whole tables: rsx_linear_rows_fwd / rsx_linear_bwd;
 * the behaviour-guided purifier and the behaviour-aware fuser: rsx.mgcn_fuse
   (csrc/mgcn.hip);
-* the UI backbone (`_PropMean` / `_PropMeanRows`) and the item views (`SF.view_prop`);
+* the UI backbone (`rsx.blocks.ui_backbone`) and the item views (`SF.view_prop`);
 * BPR + InfoNCE on the batch rows: `SF.smore_loss_rows` with the temperature 0.2 of
   mgcn.py:250 (`self.tau` is unused there and here);
 * evaluation: the fused full-sort on the cached eval-mode tables.
@@ -30,11 +30,10 @@ from . import _lib as L
 from . import mgcn_fuse as MF
 from . import ops
 from . import smore_fuse as SF
-from .bm3 import _Project
+from .blocks import _BatchIndex, _DevGraph, _ego, _join_tables, _Project, _RowsOff, cached_knn, ui_backbone
 from .lightgcn import _BprLoss
 from .nn import RsxLinear
-from .recommender import GeneralRecommender
-from .smore import SMORE, _DevGraph, _ego, _join_tables, _PropMean, _PropMeanRows, _RowsOff, _RowTags
+from .recommender import EvalTables, GeneralRecommender
 
 CL_TEMPERATURE = 0.2  # mgcn.py:250-251
 
@@ -43,7 +42,7 @@ def unsupported(what: str) -> RuntimeError:
     return RuntimeError(f"RSX_ERR_UNSUPPORTED: {what} (MGCN runs on the HIP path only)")
 
 
-class MGCN(GeneralRecommender):
+class MGCN(EvalTables, GeneralRecommender):
     # a training batch has no host syncs; no per-epoch buffer rebuilds: the Trainer may
     # capture it in a HIP graph and keep the captured steps across epochs
     supports_graph_step = True
@@ -61,11 +60,7 @@ class MGCN(GeneralRecommender):
         self.check_config(config)
         super().__init__(config, dataset)
         ops.require_device(self.device)
-        for name, f in (("image", self.v_feat), ("text", self.t_feat)):
-            if f is None:
-                raise unsupported(f"no {name} feature file: MGCN's forward needs both modalities")
-            if f.shape[1] % 4:
-                raise unsupported(f"{name} feature width {f.shape[1]} is not a multiple of 4")
+        self.require_features(unsupported, need=2)
         self.sparse = True
         self.cl_loss = config["cl_loss"]
         self.n_ui_layers = config["n_ui_layers"]
@@ -98,11 +93,11 @@ class MGCN(GeneralRecommender):
         if self.knn_mode not in ("device", "host"):
             raise ValueError(f"rsx_knn must be 'device' or 'host', got {self.knn_mode!r}")
         self.image_embedding = nn.Embedding.from_pretrained(self.v_feat.clone(), freeze=False)
-        self.image_graph = _DevGraph(*self._cached_knn(root, "image", self.v_feat, self.knn_k), ni, ni, self.device,
-                                     kchunk)
+        self.image_graph = _DevGraph(*cached_knn(root, "image", self.v_feat, self.knn_k, self.sparse, self.knn_mode,
+                                                 self.device), ni, ni, self.device, kchunk)
         self.text_embedding = nn.Embedding.from_pretrained(self.t_feat.clone(), freeze=False)
-        self.text_graph = _DevGraph(*self._cached_knn(root, "text", self.t_feat, self.knn_k), ni, ni, self.device,
-                                    kchunk)
+        self.text_graph = _DevGraph(*cached_knn(root, "text", self.t_feat, self.knn_k, self.sparse, self.knn_mode,
+                                                self.device), ni, ni, self.device, kchunk)
         self.image_trs = nn.Linear(self.v_feat.shape[1], d)
         self.text_trs = nn.Linear(self.t_feat.shape[1], d)
         self.softmax = nn.Softmax(dim=-1)
@@ -115,13 +110,10 @@ class MGCN(GeneralRecommender):
         # training loss on the batch rows only (rsx_mgcn_batch_rows: False = full tables)
         flag = config.get("rsx_mgcn_batch_rows", True)
         self.batch_rows = bool(flag if flag is not None else True)
-        self._bidx = {}
+        self._bidx = _BatchIndex(self.device)
         self._rows_off = _RowsOff(self.n_users, self.device)
         self._tags = None
-        self._eval_cache = None
         self.to(self.device)
-
-    _cached_knn = SMORE._cached_knn  # reads self.sparse / knn_mode / device only
 
     # --------------------------------------------------------------- forward
     def _views(self, rows=None):
@@ -131,14 +123,8 @@ class MGCN(GeneralRecommender):
         image_feats = _Project.apply(self.image_embedding.weight, self.image_trs.weight, self.image_trs.bias)
         text_feats = _Project.apply(self.text_embedding.weight, self.text_trs.weight, self.text_trs.bias)
         img_i, txt_i = MF.purify(image_feats, text_feats, item_id, self.gate_v, self.gate_t)
-        ego = _ego(self.user_embedding.weight, item_id)
-        if rows is not None and 1 <= self.n_ui_layers <= 4:
-            if self._tags is None:
-                self._tags = _RowTags(self.n_users + self.n_items, self.device)
-            self._tags.mark(rows)
-            content = _PropMeanRows.apply(ego, self.norm_adj_csr, self.n_ui_layers, self._tags, rows)
-        else:
-            content = _PropMean.apply(ego, self.norm_adj_csr, self.n_ui_layers)
+        content = ui_backbone(self, _ego(self.user_embedding.weight, item_id), self.norm_adj_csr, self.n_ui_layers,
+                              rows)
         image_embeds = SF.view_prop(img_i, self.image_graph, self.R, self.n_layers, self.n_users)
         text_embeds = SF.view_prop(txt_i, self.text_graph, self.R, self.n_layers, self.n_users)
         return content, image_embeds, text_embeds
@@ -157,21 +143,12 @@ class MGCN(GeneralRecommender):
         return users, items
 
     # ------------------------------------------------------------------ loss
-    def _batch_index(self, B: int):
-        """(ar, trip): arange(B) and the compact triplets (b, b, B + b) of the batch rows
-        [users; B + positives; 2B + negatives] (cached per batch size)."""
-        c = self._bidx.get(B)
-        if c is None:
-            ar = torch.arange(B, dtype=torch.int64, device=self.device)
-            c = self._bidx[B] = (ar, torch.stack([ar, ar, ar + B]).contiguous())
-        return c
-
     def calculate_loss(self, interaction):
         B = interaction.shape[1]
         if self.batch_rows:
             # the fuser is row-local and the loss reads all / side / content at the batch's
             # users, positives and negatives alone: its other rows are never computed
-            ar, trip = self._batch_index(B)
+            ar, trip = self._bidx[B]
             rows = self._rows_off.rows(interaction[:3])
             content, image_embeds, text_embeds = self._views(rows)
             all_c, side_c, content_c = MF.fuse_rows(self, content, image_embeds, text_embeds, rows)
@@ -187,18 +164,5 @@ class MGCN(GeneralRecommender):
 
     # ------------------------------------------------------------ evaluation
     def full_sort_predict(self, interaction):
-        with torch.no_grad():
-            u, i = self.forward(self.norm_adj_csr)
-        return ops.score_dense(u.contiguous(), interaction[0].contiguous(), i.contiguous())
-
-    def full_sort_topk(self, interaction, k, eval_data):
-        with torch.no_grad():
-            if self._eval_cache is None:
-                u, i = self.forward(self.norm_adj_csr)
-                self._eval_cache = (u.contiguous(), i.contiguous())
-            u, i = self._eval_cache
-        return ops.fullsort_topk(u, interaction[0].contiguous(), i, eval_data.mask_rowptr, eval_data.mask_col, k)
-
-    def train(self, mode: bool = True):
-        self._eval_cache = None
-        return super().train(mode)
+        u, i = self._eval_tables()  # not the cached tables: a forward per call
+        return ops.score_dense(u, interaction[0].contiguous(), i)

@@ -55,6 +55,29 @@ def require_single_gpu(config, unsupported) -> None:
         raise unsupported(f"torch.distributed world size {dist.get_world_size()} > 1")
 
 
+def _world():
+    import torch.distributed as dist
+
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_world_size(), dist.get_rank()
+    return 1, 0
+
+
+def loss_workspace(ws_bytes_fn, batch: int, d: int, device, unsupported) -> torch.Tensor:
+    """The workspace of a model's fused loss (`ws_bytes_fn`: its rsx_*_ws_bytes); 0 bytes is a
+    shape the kernels are not built for, refused with the model's own `unsupported(what)`."""
+    n = ws_bytes_fn(int(batch), int(d))
+    if n == 0:
+        raise unsupported(f"batch {batch}, embedding_size {d}")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def grow_workspace(ws_bytes_fn, ws: torch.Tensor, batch: int, d: int) -> torch.Tensor:
+    """`ws`, or a larger one when this batch (one above the config's) needs more."""
+    n = ws_bytes_fn(int(batch), int(d))
+    return ws if n <= ws.numel() else torch.empty(n, dtype=torch.uint8, device=ws.device)
+
+
 # ---------------------------------------------------------------------------
 # CSR adjacency + schedule
 # ---------------------------------------------------------------------------
@@ -642,6 +665,21 @@ def adj_build(u, i, n_users: int, n_items: int, mode: int, device):
                               _p(col), _p(val), _p(ws), ws.numel(), _stream()), "rsx_adj_build")
     nnz = int(rowptr[-1].item())
     return rowptr, col[:nnz], val[:nnz]
+
+
+def knn_lists(x: torch.Tensor, k: int):
+    """(values f32, idx int64, weights f32), each [n, k] on the device, of rsx_knn_graph
+    (csrc/knn.hip) on the contiguous f32 table x [n, f]: every row's top-k cosine similarities
+    in rank order, their columns (self included) and the sym-normalised values of that graph.
+    The callers check k, n and f first and raise their own errors."""
+    n, f = x.shape
+    lib = L.lib()
+    v = torch.empty(n, k, dtype=torch.float32, device=x.device)
+    i = torch.empty(n, k, dtype=torch.int64, device=x.device)
+    w = torch.empty(n, k, dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(int(lib.rsx_knn_ws_bytes(n, f)), 4), dtype=torch.uint8, device=x.device)
+    L.check(lib.rsx_knn_graph(_p(x), n, f, k, _p(v), _p(i), _p(w), _p(ws), ws.numel(), _stream()), "rsx_knn_graph")
+    return v, i, w
 
 
 def edge_dropout_build(e_u, e_i, keep, n_users: int, n_items: int, t_rowptr, t_col, t_eid):

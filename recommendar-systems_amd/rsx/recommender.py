@@ -20,6 +20,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import ops
+
 
 class AbstractRecommender(nn.Module):
     supports_fused_step = False
@@ -64,3 +66,44 @@ class GeneralRecommender(AbstractRecommender):
             if os.path.isfile(tf):
                 self.t_feat = torch.from_numpy(np.load(tf)).type(torch.FloatTensor).to(self.device)
             assert self.v_feat is not None or self.t_feat is not None, "Features all NONE"
+
+    def require_features(self, unsupported, need: int = 1, vision: str = "image") -> None:
+        """The feature-table checks of the multimodal HIP models, refused with the model's own
+        `unsupported(what)`: fewer tables than the `need` (0, 1 or 2) its forward takes, or a
+        width that is no multiple of 4 (the projection kernels read float4 rows)."""
+        if need == 1 and self.v_feat is None and self.t_feat is None:
+            raise unsupported("no feature file at all")
+        for name, f in ((vision, self.v_feat), ("text", self.t_feat)):
+            if f is None and need == 2:
+                raise unsupported(f"no {name} feature file: {type(self).__name__}'s forward needs both modalities")
+            if f is not None and f.shape[1] % 4:
+                raise unsupported(f"{name} feature width {f.shape[1]} is not a multiple of 4")
+
+
+class EvalTables:
+    """Full-sort evaluation on the eval-mode (user table, item table), computed once per
+    eval() session and kept in `_eval_cache` until train() (a mixin in front of
+    GeneralRecommender)."""
+    _eval_cache = None
+
+    def _eval_tables(self):
+        with torch.no_grad():
+            u, i = self.forward(self.norm_adj_csr)
+        return u.contiguous(), i.contiguous()
+
+    def _cached_eval_tables(self):
+        if self._eval_cache is None:
+            self._eval_cache = self._eval_tables()
+        return self._eval_cache
+
+    def full_sort_predict(self, interaction):
+        u, i = self._cached_eval_tables()
+        return ops.score_dense(u, interaction[0].contiguous(), i)
+
+    def full_sort_topk(self, interaction, k, eval_data):
+        u, i = self._cached_eval_tables()
+        return ops.fullsort_topk(u, interaction[0].contiguous(), i, eval_data.mask_rowptr, eval_data.mask_col, k)
+
+    def train(self, mode: bool = True):
+        self._eval_cache = None
+        return super().train(mode)

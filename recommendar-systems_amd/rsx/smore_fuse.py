@@ -400,7 +400,7 @@ def view_prop3(xs, Gs, R, n_layers, n_users, comm=None, tags=None, gtags=None, r
     layer for all three graphs, one for the three R products).  With `comm` (R = this
     rank's user rows) the item rows' gradients are summed over the ranks in one
     all-reduce before the item-graph backward.  With `tags` (the batch-row tags of the
-    training loss, rsx.smore._RowTags over [users; items], already marked) the user rows
+    training loss, rsx.blocks._RowTags over [users; items], already marked) the user rows
     are computed on the tagged users only: the preference block reads no other user row
     of a view.  With `gtags` (a _RowTags of its own) and `rows` the backward takes the
     incoming gradients as defined on `rows` only (preference_rows(sparse_grads=True))

@@ -170,7 +170,7 @@ def _(rowptr, col, val, x, n_cols):
 @torch.library.custom_op("rsx::propagate_mean", mutates_args=(), device_types="cuda")
 def propagate_mean(rowptr: Tensor, col: Tensor, val: Tensor, x: Tensor, n_layers: int) -> Tensor:
     """LightGCN.forward's layer mean (reference lightgcn.py:117-130) for a symmetric A."""
-    from .smore import _prop_mean
+    from .blocks import _prop_mean
 
     return _prop_mean(_csr(rowptr, col, val, _n_rows(rowptr)), x.contiguous(), int(n_layers))
 

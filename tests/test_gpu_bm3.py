@@ -341,7 +341,7 @@ def test_init_graph_and_first_step_vs_reference(cuda, tmp_path):
     for n in R.NAMES:
         assert np.array_equal(sd[n].detach().cpu().numpy().view(np.int32), z["init." + n].view(np.int32)), n
     # the two tables are adjacent in one buffer: the ego table is no copy
-    from rsx.smore import _ego
+    from rsx.blocks import _ego
 
     ego = _ego(m.user_embedding.weight, m.item_id_embedding.weight)
     assert ego.data_ptr() == m.user_embedding.weight.data_ptr() and ego.shape == (600, 64)

@@ -164,7 +164,7 @@ def test_prop_mean_rows_vs_dense(cuda, K, d):
     for bit on the batch rows; its Horner backward from a gradient that is zero off
     the batch rows equals the dense backward within f32 reassociation."""
     from rsx import graph, ops, synth
-    from rsx.smore import _PropMean, _PropMeanRows, _RowTags
+    from rsx.blocks import _PropMean, _PropMeanRows, _RowTags
 
     df = synth.amazon_like(2500, 700, 25000, seed=11)
     tr = df[df.x_label == 0]
@@ -524,7 +524,7 @@ def test_knn_graph_device_vs_host(cuda, golden, src):
     neighbours except where the host's cosine similarities of the swapped items tie
     with the k-th within 1e-5 (the GEMMs add in another order), and the normalised
     values of the common edges within rtol 2e-5."""
-    from rsx.smore import knn_graph, knn_graph_device
+    from rsx.blocks import knn_graph, knn_graph_device
 
     if src == "random":
         f = np.random.default_rng(3).standard_normal((1500, 768)).astype(np.float32)

@@ -254,7 +254,7 @@ def test_preference_rows_plan_equals_scan(cuda, d, monkeypatch):
 
 def test_view_prop_vs_torch(cuda):
     from rsx import smore_fuse as SF
-    from rsx.smore import _DevGraph
+    from rsx.blocks import _DevGraph
 
     rng = np.random.default_rng(3)
     nu, ni, d = 300, 200, 64
@@ -298,7 +298,7 @@ def test_view_prop3_equals_three_view_props(cuda, d, L_):
     separate view_prop chains bit for bit, forward and backward, on graphs with hub
     rows (in-launch fixups)."""
     from rsx import smore_fuse as SF
-    from rsx.smore import _DevGraph
+    from rsx.blocks import _DevGraph
 
     rng = np.random.default_rng(7 + d + L_)
     nu, ni = 900, 400
@@ -330,7 +330,7 @@ def test_view_prop3_tagged_users(cuda, d):
     for an upstream gradient that is zero off the tagged users (the batch-row preference
     block's); kNN graphs in 64-wide work items."""
     from rsx import smore_fuse as SF
-    from rsx.smore import _DevGraph, _RowTags
+    from rsx.blocks import _DevGraph, _RowTags
 
     rng = np.random.default_rng(d)
     nu, ni = 1200, 500
@@ -385,7 +385,7 @@ def test_view_prop3_sparse_gradients_read_only_the_batch_rows(cuda, d):
     dense backward's for the same gradient zero off the batch rows (users gathered through
     x_tag, items added through the item block's row tags); repeated batch rows."""
     from rsx import smore_fuse as SF
-    from rsx.smore import _DevGraph, _RowTags
+    from rsx.blocks import _DevGraph, _RowTags
 
     rng = np.random.default_rng(11 + d)
     nu, ni = 1100, 450

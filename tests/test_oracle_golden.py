@@ -163,7 +163,7 @@ def test_reference_knn_cache_is_read(golden, tmp_path):
     """SMORE reads the kNN cache the reference writes (smore.py:46-47,56-62: torch.save of
     the sparse [n_items, n_items] graph) through the safe loader; the graph it returns is
     the reference's own, and the product's host build (knn_graph) equals it too."""
-    from rsx.smore import knn_graph, load_reference_knn
+    from rsx.blocks import knn_graph, load_reference_knn
 
     z = golden("smore_small")
     ni = int(z["n_items"])

@@ -207,7 +207,7 @@ def main():
     names = ("prop_fwd", "proj_fwd", "loss_fwd_bwd", "proj_bwd", "prop_bwd", "adam")
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
     acc = np.zeros(len(names))
-    from rsx.smore import _ego, _PropMean
+    from rsx.blocks import _ego, _Project, _PropMean
 
     n_split = args.warmup + args.steps
     for it in range(n_split):
@@ -216,8 +216,8 @@ def main():
         ev[0].record()
         Eo = _PropMean.apply(_ego(m.user_embedding.weight, m.item_id_embedding.weight), m.norm_adj_csr, m.n_layers)
         ev[1].record()
-        To = bm3._Project.apply(m.text_embedding.weight, m.text_trs.weight, m.text_trs.bias)
-        Vo = bm3._Project.apply(m.image_embedding.weight, m.image_trs.weight, m.image_trs.bias)
+        To = _Project.apply(m.text_embedding.weight, m.text_trs.weight, m.text_trs.bias)
+        Vo = _Project.apply(m.image_embedding.weight, m.image_trs.weight, m.image_trs.bias)
         ev[2].record()
         lv = [x.detach().requires_grad_() for x in (Eo, To, Vo)]
         m._drop_seed.add_(1)

@@ -138,9 +138,8 @@ def main():
     if args.repeats < 5:
         raise SystemExit("freedom_step_time: at least 5 windows")
     from rsx import freedom
-    from rsx.bm3 import _Project
+    from rsx.blocks import _ego, _Project, ui_backbone
     from rsx.optim import RsxAdam
-    from rsx.smore import _ego, _PropMeanRows, _RowTags
     from rsx.trainer import Trainer
 
     fused = freedom._FreedomLoss
@@ -210,8 +209,6 @@ def main():
     acc = np.zeros(len(names))
     leaf = lambda *xs: [None if x is None else x.detach().requires_grad_() for x in xs]  # noqa: E731
     off = torch.cat([torch.zeros(B, dtype=torch.int64), torch.full((2 * B,), nu)]).cuda()
-    if m._tags is None:
-        m._tags = _RowTags(nu + ni, m.device)
 
     def one_step(it, record):
         opt_feat.zero_grad(set_to_none=True)
@@ -219,9 +216,7 @@ def main():
         trip = batches[it % len(batches)]
         rows = trip.reshape(-1) + off
         ev[0].record()
-        m._tags.mark(rows)
-        Et = _PropMeanRows.apply(_ego(m.user_embedding.weight, m.item_id_embedding.weight), m.train_adj, m.n_ui_layers,
-                                 m._tags, rows)
+        Et = ui_backbone(m, _ego(m.user_embedding.weight, m.item_id_embedding.weight), m.train_adj, m.n_ui_layers, rows)
         ev[1].record()
         Ht = m._item_prop()
         ev[2].record()

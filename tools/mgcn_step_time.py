@@ -161,7 +161,7 @@ def main():
     from rsx import mgcn
     from rsx import mgcn_fuse as MF
     from rsx import smore_fuse as SF
-    from rsx.smore import _ego, _PropMeanRows
+    from rsx.blocks import _ego, _Project, ui_backbone
     from rsx.trainer import Trainer
 
     tm = Timer(args)
@@ -230,21 +230,18 @@ def main():
     for it in range(args.warmup + args.steps):
         opt.zero_grad(set_to_none=True)
         inter = batches[it % len(batches)]
-        ar, trip = m._batch_index(B)
+        ar, trip = m._bidx[B]
         rws = inter[:3].reshape(-1) + m._rows_off[B]
         ev[0].record()
-        Fi = mgcn._Project.apply(m.image_embedding.weight, m.image_trs.weight, m.image_trs.bias)
-        Ft = mgcn._Project.apply(m.text_embedding.weight, m.text_trs.weight, m.text_trs.bias)
+        Fi = _Project.apply(m.image_embedding.weight, m.image_trs.weight, m.image_trs.bias)
+        Ft = _Project.apply(m.text_embedding.weight, m.text_trs.weight, m.text_trs.bias)
         ev[1].record()
         lf = leaf(Fi, Ft)
         item_l = m.item_id_embedding.weight
         xi, xt = MF.purify(lf[0], lf[1], item_l, m.gate_v, m.gate_t)
         ev[2].record()
         lx = leaf(xi, xt)
-        if m._tags is None:
-            m._tags = mgcn._RowTags(N, m.device)
-        m._tags.mark(rws)
-        content = _PropMeanRows.apply(_ego(m.user_embedding.weight, item_l), m.norm_adj_csr, m.n_ui_layers, m._tags, rws)
+        content = ui_backbone(m, _ego(m.user_embedding.weight, item_l), m.norm_adj_csr, m.n_ui_layers, rws)
         ie = SF.view_prop(lx[0], m.image_graph, m.R, m.n_layers, m.n_users)
         te = SF.view_prop(lx[1], m.text_graph, m.R, m.n_layers, m.n_users)
         ev[3].record()
