@@ -1530,6 +1530,102 @@ int rsx_lattice_graph_bwd(const rsx_lattice_graph_args* g, int32_t n_layers, con
                           const float* const* X, int32_t d, float* gF0, float* gF1, float* g_modal_weight,
                           void* ws, size_t ws_bytes, rsx_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* LGMRec: table-wide InfoNCE, hyperedge assignments, hypergraph, loss (lgmrec.hip) */
+/* ------------------------------------------------------------------------ */
+/*
+ * The InfoNCE of reference src/models/lgmrec.py:159-166 without the B x N matrix.  With
+ * n1_b = normalize(T1[idx_b]), m_j = normalize(T2[j]) (x / max(|x|, 1e-12)), ttl_b = sum_j exp(<n1_b, m_j> / tau):
+ *   out[0] = sum_b (log ttl_b - <n1_b, m_idx_b> / tau)
+ * The table is normalised once into ws; the B x N scores are tiled over the grid on the f32
+ * MFMA as exp((s - 1) / tau), the shift added back in the log domain; row sums of the table
+ * chunks are added in index order.  rsx_lgm_ssl_bwd (after rsx_lgm_ssl_fwd with the same args
+ * and ws, which it reads) writes EVERY row of gT1 and gT2 [n, d]: with P_bj = exp(s_bj / tau) / ttl_b,
+ *   d n1_b = go / tau (sum_j P_bj m_j - m_idx_b),  d m_j = go / tau (sum_b P_bj n1_b - sum_{b: idx_b = j} n1_b)
+ * through the normalisations' Jacobians.  T1 == T2 (one table) needs gT1 == gT2 and both sums
+ * land in that buffer; otherwise gT1 is zero off the rows of idx.  Repeats in idx are summed by
+ * the first-occurrence walk; no float atomics, bit-identical from run to run.  An index outside
+ * [0, n) contributes nothing.  d in {64, 128}, batch <= 65536, n < 2^31, else
+ * RSX_ERR_UNSUPPORTED (rsx_lgm_ssl_ws_bytes: 0).  No allocation or synchronisation.
+ */
+typedef struct rsx_lgm_ssl_args {
+    const float* T1;    /* [n, d] the table the batch rows come from */
+    const float* T2;    /* [n, d] the table scored against (may be T1) */
+    const int64_t* idx; /* [batch] rows, repeats allowed */
+    int64_t n, batch;
+    int32_t d;          /* 64 or 128 */
+    float tau;
+} rsx_lgm_ssl_args;
+size_t rsx_lgm_ssl_ws_bytes(int64_t n, int64_t batch, int32_t d);
+int rsx_lgm_ssl_fwd(const rsx_lgm_ssl_args* a, float* out, void* ws, size_t ws_bytes, rsx_stream_t stream);
+int rsx_lgm_ssl_bwd(const rsx_lgm_ssl_args* a, const float* go, float* gT1, float* gT2, void* ws, size_t ws_bytes,
+                    rsx_stream_t stream);
+
+/*
+ * The hyperedge assignments (lgmrec.py:118-126, 139-140): on logits x [n, H] of row stride ld,
+ *   y = softmax((x + g) / tau) over the H columns,  out = y keep / keep_rate
+ * g: the float32 Gumbel noise [n, H] when given, else -log(-log u) of a 32-bit hash of
+ * (*seed, stream_id, row, column): u = (k + 1/2) 2^-23, k the hash's top 23 bits, exact in
+ * float32, so u is in [2^-24, 1 - 2^-24] and g is finite (rsx_lgm_gumbel_of_bits is that map, on
+ * the host).  keep: the packed mask (bit h % 32 of word [row, h / 32]) when given, else hashed
+ * the same way when keep_rate < 1, else all ones.  y and out have row stride ld and are two
+ * buffers; columns past H are neither read nor written.  noise_out (optional, [n, H])
+ * receives the noise used.  rsx_lgm_assign_bwd: dx = y (dy' - sum_h y_h dy'_h) / tau with
+ * dy' = dy keep / keep_rate, from the same args.  H a multiple of 4 in 4..64.
+ */
+typedef struct rsx_lgm_assign_args {
+    const float* x;       /* [n, ld] logits */
+    const float* noise;   /* [n, H] or NULL */
+    const uint32_t* keep; /* [n, ceil(H / 32)] or NULL */
+    const int64_t* seed;  /* device word: needed when a draw is hashed, else may be NULL */
+    int64_t n;
+    int32_t H, ld, stream_id;
+    float tau, keep_rate;
+    int32_t pad0;
+} rsx_lgm_assign_args;
+int rsx_lgm_assign_fwd(const rsx_lgm_assign_args* a, float* y, float* out, float* noise_out, rsx_stream_t stream);
+int rsx_lgm_assign_bwd(const rsx_lgm_assign_args* a, const float* y, const float* dy, float* dx, rsx_stream_t stream);
+float rsx_lgm_gumbel_of_bits(uint32_t bits);
+
+/*
+ * The tall-skinny products of HGNNLayer (lgmrec.py:202-214), P [n, H] of row stride ld, H <= 64,
+ * d in {64, 128}:
+ *   rsx_lgm_hgnn_reduce   lat [H, d] = P^T X (+ P2^T X2 when n2 > 0): parts of at least 128 rows, added in index order
+ *   rsx_lgm_hgnn_expand   Y [n, d] = P lat (lat held in LDS)
+ *   rsx_lgm_hgnn_rowdots  G [n, H] (row stride ld) = X lat^T, added to G when accumulate != 0
+ * A layer's backward is these three.  Deterministic, no atomics.
+ */
+size_t rsx_lgm_hgnn_ws_bytes(int64_t n, int64_t n2, int32_t H, int32_t d);
+int rsx_lgm_hgnn_reduce(const float* P, const float* X, int64_t n, const float* P2, const float* X2, int64_t n2,
+                        int32_t ld, int32_t H, int32_t d, float* lat, void* ws, size_t ws_bytes, rsx_stream_t stream);
+int rsx_lgm_hgnn_expand(const float* P, int32_t ld, int32_t H, const float* lat, int64_t n, int32_t d, float* Y,
+                        rsx_stream_t stream);
+int rsx_lgm_hgnn_rowdots(const float* X, const float* lat, int32_t H, int64_t n, int32_t d, float* G, int32_t ld,
+                         int32_t accumulate, rsx_stream_t stream);
+
+/*
+ * The loss (lgmrec.py:175-194 without the ssl terms).  On the batch's 3 B rows of
+ *   all = C + normalize(Mv) + normalize(Mt) + alpha normalize(Gv + Gt)   (tables [n_users + n_items, d])
+ * out = {bpr + reg, bpr, reg}: bpr = mean softplus(-(<u, p> - <u, n>)),
+ * reg = reg_weight (|U|_F + |P|_F + |N|_F) / batch, the Frobenius norms of the [batch, d] matrices.
+ * rsx_lgm_loss_bwd (after rsx_lgm_loss_fwd with the same args and ws: it reads the norms) writes
+ * EVERY row of the five gradient tables, zero off the batch rows; rows repeated in the batch
+ * are summed by the first-occurrence walk; a zero Frobenius norm gives a zero gradient.
+ * Limits and errors as rsx_lattice_loss_*.
+ */
+typedef struct rsx_lgm_loss_args {
+    const float *C, *Mv, *Mt, *Gv, *Gt;
+    const int64_t* triplets; /* [3, batch] users, positives, negatives (item ids, not offset) */
+    int64_t n_users, n_items, batch;
+    int32_t d;
+    float alpha, reg;
+    int32_t pad0;
+} rsx_lgm_loss_args;
+size_t rsx_lgm_loss_ws_bytes(int64_t batch, int32_t d);
+int rsx_lgm_loss_fwd(const rsx_lgm_loss_args* a, float* out, void* ws, size_t ws_bytes, rsx_stream_t stream);
+int rsx_lgm_loss_bwd(const rsx_lgm_loss_args* a, const float* go, float* gC, float* gMv, float* gMt, float* gGv,
+                     float* gGt, void* ws, size_t ws_bytes, rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

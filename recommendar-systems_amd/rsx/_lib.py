@@ -133,6 +133,20 @@ class LatticeArgs(C.Structure):
                 ("d", I32), ("reg", F32), ("batch_size", F32), ("pad0", I32)]
 
 
+class LgmSslArgs(C.Structure):
+    _fields_ = [("T1", P), ("T2", P), ("idx", P), ("n", I64), ("batch", I64), ("d", I32), ("tau", F32)]
+
+
+class LgmAssignArgs(C.Structure):
+    _fields_ = [("x", P), ("noise", P), ("keep", P), ("seed", P), ("n", I64), ("H", I32), ("ld", I32),
+                ("stream_id", I32), ("tau", F32), ("keep_rate", F32), ("pad0", I32)]
+
+
+class LgmLossArgs(C.Structure):
+    _fields_ = [("C", P), ("Mv", P), ("Mt", P), ("Gv", P), ("Gt", P), ("triplets", P), ("n_users", I64),
+                ("n_items", I64), ("batch", I64), ("d", I32), ("alpha", F32), ("reg", F32), ("pad0", I32)]
+
+
 class LatticeGraph(C.Structure):
     _fields_ = [("n", I64), ("k", I32), ("n_mod", I32), ("f", I32), ("lam", F32), ("F", P * 2), ("idx", P * 2),
                 ("oidx", P * 2), ("oval", P * 2), ("modal_weight", P), ("w", P), ("invn", P * 2), ("a", P * 2),
@@ -267,6 +281,19 @@ def _declare(lib):
         "rsx_lattice_prop": (C.c_int, [C.POINTER(LatticeGraph), P, P, I32, I32, P]),
         "rsx_lattice_graph_bwd_ws_bytes": (C.c_size_t, [I64, I32, I32]),
         "rsx_lattice_graph_bwd": (C.c_int, [C.POINTER(LatticeGraph), I32, P, P, I32, P, P, P, P, C.c_size_t, P]),
+        "rsx_lgm_ssl_ws_bytes": (C.c_size_t, [I64, I64, I32]),
+        "rsx_lgm_ssl_fwd": (C.c_int, [C.POINTER(LgmSslArgs), P, P, C.c_size_t, P]),
+        "rsx_lgm_ssl_bwd": (C.c_int, [C.POINTER(LgmSslArgs), P, P, P, P, C.c_size_t, P]),
+        "rsx_lgm_assign_fwd": (C.c_int, [C.POINTER(LgmAssignArgs), P, P, P, P]),
+        "rsx_lgm_assign_bwd": (C.c_int, [C.POINTER(LgmAssignArgs), P, P, P, P]),
+        "rsx_lgm_gumbel_of_bits": (C.c_float, [C.c_uint32]),
+        "rsx_lgm_hgnn_ws_bytes": (C.c_size_t, [I64, I64, I32, I32]),
+        "rsx_lgm_hgnn_reduce": (C.c_int, [P, P, I64, P, P, I64, I32, I32, I32, P, P, C.c_size_t, P]),
+        "rsx_lgm_hgnn_expand": (C.c_int, [P, I32, I32, P, I64, I32, P, P]),
+        "rsx_lgm_hgnn_rowdots": (C.c_int, [P, P, I32, I64, I32, P, I32, I32, P]),
+        "rsx_lgm_loss_ws_bytes": (C.c_size_t, [I64, I32]),
+        "rsx_lgm_loss_fwd": (C.c_int, [C.POINTER(LgmLossArgs), P, P, C.c_size_t, P]),
+        "rsx_lgm_loss_bwd": (C.c_int, [C.POINTER(LgmLossArgs), P, P, P, P, P, P, P, C.c_size_t, P]),
         "rsx_cpu_spmm": (C.c_int, [P, P, P, I64, P, I32, P]),
         "rsx_cpu_propagate_mean": (C.c_int, [P, P, P, I64, P, I32, I32, P]),
         "rsx_cpu_layergcn_forward": (C.c_int, [P, P, P, I64, P, I32, I32, P, P, P]),
@@ -308,6 +335,9 @@ EXPORTED = ["rsx_version", "rsx_csr_schedule_host", "rsx_csr_schedule_rebind", "
             "rsx_freedom_ws_bytes", "rsx_freedom_loss_fwd", "rsx_freedom_loss_bwd",
             "rsx_lattice_ws_bytes", "rsx_lattice_loss_fwd", "rsx_lattice_loss_bwd", "rsx_lattice_graph",
             "rsx_lattice_prop", "rsx_lattice_graph_bwd_ws_bytes", "rsx_lattice_graph_bwd",
+            "rsx_lgm_ssl_ws_bytes", "rsx_lgm_ssl_fwd", "rsx_lgm_ssl_bwd", "rsx_lgm_assign_fwd", "rsx_lgm_assign_bwd", "rsx_lgm_gumbel_of_bits",
+            "rsx_lgm_hgnn_ws_bytes", "rsx_lgm_hgnn_reduce", "rsx_lgm_hgnn_expand", "rsx_lgm_hgnn_rowdots",
+            "rsx_lgm_loss_ws_bytes", "rsx_lgm_loss_fwd", "rsx_lgm_loss_bwd",
             "rsx_cpu_spmm", "rsx_cpu_propagate_mean", "rsx_cpu_layergcn_forward", "rsx_cpu_layergcn_backward",
             "rsx_cpu_bpr", "rsx_cpu_fullsort_topk", "rsx_cpu_adam", "rsx_cpu_gcn_step_ws_floats", "rsx_cpu_gcn_step"]
 

@@ -11,7 +11,8 @@ import torch
 MODELS = {"lightgcn": ("rsx.lightgcn", "LightGCN"), "layergcn": ("rsx.layergcn", "LayerGCN"),
           "smore": ("rsx.smore", "SMORE"), "bpr": ("rsx.bpr", "BPR"), "vbpr": ("rsx.vbpr", "VBPR"),
           "bm3": ("rsx.bm3", "BM3"), "mgcn": ("rsx.mgcn", "MGCN"),
-          "freedom": ("rsx.freedom", "FREEDOM"), "lattice": ("rsx.lattice", "LATTICE")}
+          "freedom": ("rsx.freedom", "FREEDOM"), "lattice": ("rsx.lattice", "LATTICE"),
+          "lgmrec": ("rsx.lgmrec", "LGMRec")}
 
 
 def get_local_time():

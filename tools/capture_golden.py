@@ -16,7 +16,7 @@ modifies a reference file:
 Outputs are small `.npz` files under `tests/golden/` (data only: inputs and the
 reference's outputs). The reference itself never travels to the GPU box.
 
-Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice]
+Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec]
 """
 from __future__ import annotations
 
@@ -845,10 +845,218 @@ def capture_lattice(out_dir):
         assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
 
 
+LGMREC_OVERRIDES = dict(train_batch_size=512, eval_batch_size=256, is_multimodal_model=True, hyper_num=[4],
+                        n_hyper_layer=[1], keep_rate=[0.5], alpha=[0.3], n_ui_layers=[2], n_mm_layers=[2],
+                        cl_weight=[0.01], reg_weight=[1e-3], learning_rate=0.001, cf_model="lightgcn")
+
+
+class _LgmTap:
+    """Records, in call order, every Gumbel noise tensor F.gumbel_softmax draws (re-drawn from
+    the saved generator state and checked against its output) and every keep mask of a
+    training-mode F.dropout; `terms` collects the loss terms of models.lgmrec."""
+
+    def __init__(self):
+        import torch.nn.functional as F
+
+        self.F, self.noise, self.keep, self.terms = F, [], [], []
+        self.orig = (F.gumbel_softmax, F.dropout)
+        tap = self
+
+        def gumbel_softmax(logits, tau=1, hard=False, eps=1e-10, dim=-1):
+            state = torch.get_rng_state()
+            y = tap.orig[0](logits, tau=tau, hard=hard, dim=dim)
+            after = torch.get_rng_state()
+            torch.set_rng_state(state)
+            g = -torch.empty_like(logits).exponential_().log()
+            assert torch.equal(torch.get_rng_state(), after)
+            assert torch.equal(((logits + g) / tau).softmax(dim), y)
+            tap.noise.append(g.detach().numpy().copy())
+            return y
+
+        def dropout(x, p=0.5, training=True, inplace=False):
+            y = tap.orig[1](x, p, training, inplace)
+            if training:
+                tap.keep.append(((y != 0) | (x == 0)).numpy())
+            return y
+
+        F.gumbel_softmax, F.dropout = gumbel_softmax, dropout
+
+    def wrap_terms(self, model):
+        for name in ("bpr_loss", "ssl_triple_loss", "reg_loss"):
+            fn = getattr(model, name)
+            setattr(model, name, (lambda f: lambda *a: self.terms.append(float((r := f(*a)).detach())) or r)(fn))
+
+    def take(self):
+        """(noise list, packed keep list, terms) since the last take."""
+        out = self.noise, [_pack_bits(k) for k in self.keep], self.terms
+        self.noise, self.keep, self.terms = [], [], []
+        return out
+
+    def close(self):
+        self.F.gumbel_softmax, self.F.dropout = self.orig
+
+
+def _pack_bits(keep: np.ndarray) -> np.ndarray:
+    """bool [n, H] -> uint32 [n, ceil(H / 32)]: bit (h & 31) of word h // 32 = column h kept."""
+    n, H = keep.shape
+    out = np.zeros((n, (H + 31) // 32), np.uint32)
+    for h in range(H):
+        out[:, h // 32] |= keep[:, h].astype(np.uint32) << np.uint32(h % 32)
+    return out
+
+
+def _lgm_store_draws(out, prefix, noise, keeps):
+    for k, g in enumerate(noise):
+        out[f"{prefix}noise{k}"] = g.astype(np.float32)
+    for k, m in enumerate(keeps):
+        out[f"{prefix}keep{k}"] = m
+
+
+def _lgm_model(tap):
+    from utils.utils import init_seed, get_model
+    from common.trainer import Trainer
+
+    config, train, valid, _ = _load("LGMRec", "baby", LGMREC_OVERRIDES)
+    hp = _select_hparams(config)
+    init_seed(config["seed"])
+    train.pretrain_setup()
+    model = get_model("LGMRec")(config, train)
+    tap.wrap_terms(model)
+    return config, hp, train, valid, model, Trainer(config, model)
+
+
+def capture_lgmrec(out_dir):
+    """LGMRec (reference src/models/lgmrec.py) on the small graph and the 48 / 24-wide synthetic
+    features of the other fixtures: seed 999, hyper_num 4, one hypergraph layer, keep_rate 0.5,
+    alpha 0.3, two UI and two modality layers, cl_weight 0.01, reg_weight 1e-3, batches of 512.
+    scipy's dok_matrix no longer has the `_update` lgmrec.py:76 calls: it is supplied while the
+    tool runs (a loop of A[row, col] = value).
+    lgmrec_step0_small.npz: the initial parameters, norm_adj and num_inters, one evaluation-mode
+    forward with its noise (the user and item outputs and every eighth row of the two
+    hypergraph tables), the first two training steps (triplets, draws, loss terms bpr, ssl_u,
+    ssl_i, reg, gradients, parameters after Adam as XOR with `init.*`).
+    lgmrec_small.npz: the interactions and features, one epoch through the reference's Trainer
+    with every step's draws, the parameters after it (XOR), and the reference's scores and
+    top-50 for its first two evaluation batches with their noise."""
+    import scipy.sparse as sp
+
+    shutil.rmtree(os.path.join(DATA_ROOT, "baby"), ignore_errors=True)
+    df = synth.amazon_like(400, 200, 4000, seed=7)
+    synth.write_inter(df, DATA_ROOT, "baby")
+    n_items = int(df.itemID.max()) + 1
+    np.save(os.path.join(DATA_ROOT, "baby", "image_feat_raw.npy"), synth.features(n_items, 48, seed=11))
+    np.save(os.path.join(DATA_ROOT, "baby", "text_feat_raw.npy"), synth.features(n_items, 24, seed=12))
+    had = hasattr(sp.dok_matrix, "_update")
+    if not had:
+        def _update(self, data):
+            for (r, c), v in data.items():
+                self[r, c] = v
+
+        sp.dok_matrix._update = _update
+    tap = _LgmTap()
+    xor = lambda a, b: a.view(np.int32) ^ b.view(np.int32)  # noqa: E731
+    try:
+        # ---- pass 1: the eval-mode forward and the first two steps
+        config, hp, train, valid, model, trainer = _lgm_model(tap)
+        nu = model.n_users
+        out = {"n_users": np.int64(nu), "n_items": np.int64(model.n_items)}
+        init = {n: p.numpy().copy() for n, p in _param_dict(model).items()}
+        for n, v in init.items():
+            if n not in ("image_embedding.weight", "text_embedding.weight"):  # frozen: v_feat / t_feat
+                out["init." + n] = v
+        A = model.norm_adj.coalesce()
+        out["norm_adj_idx"] = A.indices().numpy().astype(np.int16)
+        out["norm_adj_val"] = A.values().numpy().astype(np.float32)
+        out["num_inters"] = model.num_inters.numpy().astype(np.float32)
+        model.eval()
+        with torch.no_grad():
+            u, i, hyper = model.forward()
+        noise, keeps, _ = tap.take()
+        assert len(noise) == 4 and not keeps
+        _lgm_store_draws(out, "fwd_", noise, [])
+        out["fwd_user"], out["fwd_item"] = u.numpy(), i.numpy()
+        for name, t in zip(("uv", "iv", "ut", "it"), hyper):
+            out["fwd_hyper_" + name] = t.numpy()[::8].copy()
+        model.train()
+        it = iter(train)
+        for step in range(2):
+            batch = next(it)
+            trainer.optimizer.zero_grad()
+            loss = model.calculate_loss(batch)
+            loss.backward()
+            noise, keeps, terms = tap.take()
+            assert len(noise) == 4 and len(keeps) == 4 and len(terms) == 4
+            pre = f"step{step}_"
+            _lgm_store_draws(out, pre, noise, keeps)
+            out[pre + "triplets"] = batch.numpy().astype(np.int16)
+            out[pre + "loss"] = np.float64(loss.item())
+            out[pre + "terms"] = np.array(terms, dtype=np.float64)  # bpr, ssl_u, ssl_i, reg
+            out[pre + "no_grad"] = np.array([n for n, p in model.named_parameters() if p.grad is None] +
+                                            [n for n, p in model.named_parameters() if not p.requires_grad])
+            for n, p in model.named_parameters():
+                if p.grad is not None:
+                    out[pre + "grad." + n] = p.grad.numpy().copy()
+            trainer.optimizer.step()
+            for n, p in _param_dict(model).items():
+                if "init." + n in out:
+                    out[pre + "param_xor." + n] = xor(p.numpy(), init[n])
+        out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()])
+        path = os.path.join(out_dir, "lgmrec_step0_small.npz")
+        np.savez_compressed(path, **out)
+        print(f"wrote {path}: {os.path.getsize(path) / 1e6:.2f} MB, keys={len(out)}")
+
+        # ---- pass 2: one epoch through the reference's Trainer, then its first two eval batches
+        config, hp, train, valid, model, trainer = _lgm_model(tap)
+        for n, v in init.items():
+            assert np.array_equal(dict(_param_dict(model))[n].numpy(), v), n
+        out = {"n_users": np.int64(nu), "n_items": np.int64(model.n_items)}
+        inter = train.inter_matrix(form="coo")
+        out["train_u"], out["train_i"] = inter.row.astype(np.int16), inter.col.astype(np.int16)
+        out["v_feat"], out["t_feat"] = model.v_feat.numpy().copy(), model.t_feat.numpy().copy()
+        rec = _Recorder(train)
+        model.pre_epoch_processing()
+        loss_sum, _ = trainer._train_epoch(train, 0)
+        noise, keeps, terms = tap.take()
+        nb = len(rec.batches)
+        assert len(noise) == 4 * nb and len(keeps) == 4 * nb
+        out["epoch0_triplets"] = torch.cat(rec.batches, dim=1).numpy().astype(np.int16)
+        out["epoch0_nbatch"] = np.int64(nb)
+        out["epoch0_loss"] = np.float64(float(loss_sum))
+        for b in range(nb):
+            _lgm_store_draws(out, f"epoch0_b{b}_", noise[4 * b: 4 * b + 4], keeps[4 * b: 4 * b + 4])
+        for n, p in _param_dict(model).items():
+            if n not in ("image_embedding.weight", "text_embedding.weight"):
+                out["epoch0_param_xor." + n] = xor(p.numpy(), init[n])
+        model.eval()
+        k = max(config["topk"])
+        with torch.no_grad():
+            for b, batch in zip(range(2), valid):
+                scores = model.full_sort_predict(batch)
+                noise, keeps, _ = tap.take()
+                assert len(noise) == 4 and not keeps
+                _lgm_store_draws(out, f"eval_b{b}_", noise, [])
+                out[f"eval_b{b}_users"] = batch[0].numpy().astype(np.int16)
+                out[f"eval_b{b}_scores"] = scores.numpy().astype(np.float32)
+                masked = scores.clone()
+                masked[batch[1][0], batch[1][1]] = -1e10
+                out[f"eval_b{b}_mask"] = batch[1].numpy().astype(np.int16)
+                out[f"eval_b{b}_topk_idx"] = _topk_with_ties(masked, k)[1].numpy().astype(np.int16)
+        out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()])
+        path = os.path.join(out_dir, "lgmrec_small.npz")
+        np.savez_compressed(path, **out)
+        print(f"wrote {path}: {os.path.getsize(path) / 1e6:.2f} MB, keys={len(out)}")
+    finally:
+        tap.close()
+        if not had:
+            del sp.dok_matrix._update
+    for f in ("lgmrec_small.npz", "lgmrec_step0_small.npz"):
+        assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice")
+    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     _install_shims()
@@ -861,6 +1069,9 @@ def main():
         return
     if args.only == "lattice":
         capture_lattice(args.out)
+        return
+    if args.only == "lgmrec":
+        capture_lgmrec(args.out)
         return
     if args.only == "mf":
         capture_mf(args.out)
