@@ -13,10 +13,13 @@ modifies a reference file:
    `src/models/mgcn.py:59,69`, `src/models/lattice.py:76,87`);
 4. `torch_scatter.scatter_add` is restated with `index_add_` (`src/utils/utils.py:140`).
 
+GRCN adds a fifth for its own capture: `torch_geometric` as far as `src/models/grcn.py` uses it
+(`_install_pyg_shim`).
+
 Outputs are small `.npz` files under `tests/golden/` (data only: inputs and the
 reference's outputs). The reference itself never travels to the GPU box.
 
-Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec]
+Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn]
 """
 from __future__ import annotations
 
@@ -1053,10 +1056,215 @@ def capture_lgmrec(out_dir):
         assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
 
 
+GRCN_OVERRIDES = dict(train_batch_size=512, eval_batch_size=256, is_multimodal_model=True, learning_rate=[0.001],
+                      reg_weight=[0.001])
+GRCN_ROWS = dict(rep=8, grad=2, param=4, epoch=8, last=4)  # the row strides the tables are stored at
+
+
+def _install_pyg_shim():
+    """torch_geometric as far as src/models/grcn.py uses it (harness only, our own code):
+    MessagePassing with aggr 'add' and the source -> target flow, PyG's softmax,
+    remove_self_loops / add_self_loops, and dropout_adj for p = 0."""
+    import inspect
+
+    class MessagePassing(torch.nn.Module):
+        def __init__(self, aggr="add", **kw):
+            super().__init__()
+            assert aggr == "add", aggr
+            self.aggr = aggr
+
+        def propagate(self, edge_index, size=None, x=None):
+            j, i = edge_index[0], edge_index[1]
+            have = dict(x_j=x[j], x_i=x[i], size_i=x.shape[0], edge_index_i=i)
+            names = [n for n in inspect.signature(self.message).parameters]
+            msg = self.message(**{n: have[n] for n in names})
+            out = torch.zeros(x.shape[0], msg.shape[1], dtype=msg.dtype).index_add_(0, i, msg)
+            return self.update(out)
+
+        def update(self, aggr_out):
+            return aggr_out
+
+    def softmax(src, index, num_nodes=None):
+        n = int(index.max()) + 1 if num_nodes is None else num_nodes
+        mx = torch.full((n,), -float("inf"), dtype=src.dtype).scatter_reduce(0, index, src.detach(), reduce="amax")
+        out = (src - mx[index]).exp()
+        return out / (torch.zeros(n, dtype=src.dtype).index_add_(0, index, out)[index] + 1e-16)
+
+    def remove_self_loops(edge_index, edge_attr=None):
+        keep = edge_index[0] != edge_index[1]
+        return edge_index[:, keep], None if edge_attr is None else edge_attr[keep]
+
+    def add_self_loops(edge_index, edge_attr=None, fill_value=None, num_nodes=None):
+        n = int(edge_index.max()) + 1 if num_nodes is None else num_nodes
+        loop = torch.arange(n, dtype=edge_index.dtype).repeat(2, 1)
+        return torch.cat([edge_index, loop], dim=1), edge_attr
+
+    def dropout_adj(edge_index, edge_attr=None, p=0.5, **kw):
+        if p != 0:
+            raise NotImplementedError("dropout_adj: only p = 0 is shimmed")
+        return edge_index, None
+
+    tg, nn_, conv, utils = (types.ModuleType(n) for n in ("torch_geometric", "torch_geometric.nn",
+                                                          "torch_geometric.nn.conv", "torch_geometric.utils"))
+    conv.MessagePassing = nn_.MessagePassing = MessagePassing
+    utils.softmax, utils.remove_self_loops, utils.add_self_loops = softmax, remove_self_loops, add_self_loops
+    utils.dropout_adj = dropout_adj
+    tg.nn, tg.utils, nn_.conv = nn_, utils, conv
+    for m in (tg, nn_, conv, utils):
+        sys.modules[m.__name__] = m
+
+
+def _grcn_model():
+    from utils.utils import init_seed, get_model
+    from common.trainer import Trainer
+
+    config, train, valid, test = _load("GRCN", "baby", GRCN_OVERRIDES)
+    hp = _select_hparams(config)
+    init_seed(config["seed"])
+    train.pretrain_setup()
+    model = get_model("GRCN")(config, train)
+    return config, hp, train, valid, test, model, Trainer(config, model)
+
+
+def capture_grcn(out_dir):
+    """GRCN (reference src/models/grcn.py) on the small graph and the 48 / 24-wide synthetic
+    features of the other fixtures: seed 999, the YAML's sizes (64 / 64, three routing
+    iterations), learning_rate and reg_weight 0.001, batches of 512.  torch_geometric is the
+    shim above; Tensor.cuda is the identity while the model is built and trained
+    (grcn.py:318 calls torch.zeros(1).cuda()).
+    grcn_step0_small.npz: the first two steps: triplets,
+    loss / bpr / reg, alpha_v, alpha_t and the refined weight in the reference's [2 E] order, and
+    at the row strides of GRCN_ROWS the representation, the table gradients and the tables after
+    Adam (the MLP and confidence arrays whole).
+    grcn_small.npz: the initial parameters and `result`, the training edges in the reference's
+    order, features, two epochs through the reference's Trainer with the
+    parameters after each (row strides `epoch`, `last`), the evaluation of the initial `result`
+    and of the last epoch.
+    The capture fails unless, on both steps, every edge's two confidence-weighted candidates are
+    either both <= 0 or more than 1e-5 (relative) apart: a flipped argmax is the one place where
+    float32 rounding changes a gradient discontinuously."""
+    shutil.rmtree(os.path.join(DATA_ROOT, "baby"), ignore_errors=True)
+    df = synth.amazon_like(400, 200, 4000, seed=7)
+    synth.write_inter(df, DATA_ROOT, "baby")
+    n_items = int(df.itemID.max()) + 1
+    np.save(os.path.join(DATA_ROOT, "baby", "image_feat_raw.npy"), synth.features(n_items, 48, seed=11))
+    np.save(os.path.join(DATA_ROOT, "baby", "text_feat_raw.npy"), synth.features(n_items, 24, seed=12))
+    _install_pyg_shim()
+    orig_cuda = torch.Tensor.cuda
+    torch.Tensor.cuda = lambda self, *a, **k: self
+    S = GRCN_ROWS
+    small = ("MLP.", "model_specific_conf")  # stored whole
+    rows = lambda a, n, k: a if any(s in n for s in small) else a[::k].copy()  # noqa: E731
+    try:
+        # ---- pass 1: the first two steps
+        config, hp, train, valid, test, model, trainer = _grcn_model()
+        nu, ni = model.n_users, model.n_items
+        out = {"n_users": np.int64(nu), "n_items": np.int64(ni)}
+        init = {n: p.numpy().copy() for n, p in _param_dict(model).items()}
+        init_result = model.result.numpy().copy()
+        ei = model.edge_index
+        seen = {}
+        orig_fwd = model.id_gcn.forward
+
+        def tapped(edge_index, weight_vector):
+            seen["w"] = weight_vector.detach().clone()
+            return orig_fwd(edge_index, weight_vector)
+
+        model.id_gcn.forward = tapped
+        model.train()
+        it = iter(train)
+        for step in range(2):
+            batch = next(it)
+            trainer.optimizer.zero_grad()
+            loss = model.calculate_loss(batch)
+            loss.backward()
+            pre = f"step{step}_"
+            rep = model.result.detach()
+            av, at = (g.conv_embed_1.alpha.detach().reshape(-1) for g in (model.v_gcn, model.t_gcn))
+            C_ = torch.cat([model.model_specific_conf[ei[0]], model.model_specific_conf[ei[1]]], dim=0).detach()
+            cv, ct = av * C_[:, 0], at * C_[:, 1]
+            live = (cv > 0) | (ct > 0)
+            gap = (cv - ct).abs() / torch.maximum(cv.abs(), ct.abs()).clamp_min(1e-30)
+            assert bool((gap[live] > 1e-5).all()), f"step {step}: an argmax within 1e-5: pick another feature seed"
+            out[pre + "min_gap"] = np.float64(gap[live].min())
+            u, p, n = batch[0], batch[1] + nu, batch[2] + nu
+            bpr = torch.nn.functional.softplus(-((rep[u] * rep[p]).sum(1) - (rep[u] * rep[n]).sum(1))).mean()
+            out[pre + "triplets"] = batch.numpy().astype(np.int16)
+            out[pre + "loss"] = np.float64(loss.item())
+            out[pre + "bpr"] = np.float64(bpr.item())
+            # reg itself, in float64 on the model's own parameters (the loss returns only the sum,
+            # and loss - bpr would carry the loss's float32 rounding, 1e-4 of reg); it has to
+            # account for the rest of the reference's loss to that rounding
+            ut, it_ = u.repeat_interleave(2), torch.stack([p, n]).t().reshape(-1)
+            E_, pv, pt = (t.detach().double() for t in (model.id_gcn.id_embedding, model.v_gcn.preference,
+                                                        model.t_gcn.preference))
+            reg = float(model.reg_weight) * ((E_[ut] ** 2 + E_[it_] ** 2).mean() + (pv ** 2).mean() +
+                                             (pv[ut] ** 2).mean() + (pt[ut] ** 2).mean())
+            assert abs(loss.item() - bpr.item() - reg.item()) <= 3e-7 * abs(loss.item()), (loss.item(), bpr.item(), reg.item())
+            out[pre + "reg"] = np.float64(reg.item())
+            out[pre + "alpha_v"], out[pre + "alpha_t"] = av.numpy().copy(), at.numpy().copy()
+            out[pre + "weight"] = seen["w"].reshape(-1).numpy().copy()
+            out[pre + "representation"] = rep.numpy()[::S["rep"]].copy()
+            for name, prm in model.named_parameters():
+                out[pre + "grad." + name] = rows(prm.grad.numpy(), name, S["grad"])
+            trainer.optimizer.step()
+            for name, prm in _param_dict(model).items():
+                out[pre + "param." + name] = rows(prm.numpy(), name, S["param"])
+        out["row_strides"] = np.array([f"{k}={v}" for k, v in S.items()])
+        out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()] +
+                                  [f"{k}={config[k]}" for k in ("embedding_size", "latent_embedding", "n_layers")])
+        path = os.path.join(out_dir, "grcn_step0_small.npz")
+        np.savez_compressed(path, **out)
+        print(f"wrote {path}: {os.path.getsize(path) / 1e6:.2f} MB, keys={len(out)}")
+
+        # ---- pass 2: two epochs through the reference's Trainer
+        config, hp, train, valid, test, model, trainer = _grcn_model()
+        for n, v in init.items():
+            assert np.array_equal(dict(_param_dict(model))[n].numpy(), v), n
+        assert np.array_equal(model.result.numpy(), init_result)
+        out = {"n_users": np.int64(nu), "n_items": np.int64(ni)}
+        # the training edges in the reference's own order (model.edge_index, grcn.py:191-193)
+        ei = model.edge_index.numpy()
+        out["train_u"], out["train_i"] = ei[0].astype(np.int16), (ei[1] - nu).astype(np.int16)
+        for n, v in init.items():
+            out["init." + n] = v
+        out["init.result"] = model.result.numpy().copy()
+        out["v_feat"], out["t_feat"] = model.v_feat.numpy().copy(), model.t_feat.numpy().copy()
+        rec = _Recorder(train)
+        _eval_dump(trainer, model, valid, "init_valid", out)
+        losses = []
+        for epoch in range(2):
+            model.pre_epoch_processing()
+            n0 = len(rec.batches)
+            loss_sum, _ = trainer._train_epoch(train, epoch)
+            trainer.lr_scheduler.step()
+            losses.append(float(loss_sum))
+            out[f"epoch{epoch}_triplets"] = torch.cat(rec.batches[n0:], dim=1).numpy().astype(np.int16)
+            out[f"epoch{epoch}_nbatch"] = np.int64(len(rec.batches) - n0)
+            for name, prm in _param_dict(model).items():
+                out[f"epoch{epoch}_param." + name] = rows(prm.numpy(), name, S["last" if epoch == 1 else "epoch"])
+        out["epoch_losses"] = np.array(losses)
+        _eval_dump(trainer, model, valid, "epoch1_valid", out)
+        _eval_dump(trainer, model, test, "epoch1_test", out)
+        for tag, ld in (("valid", valid), ("test", test)):
+            out[f"{tag}_eval_u"] = ld.get_eval_users().numpy().astype(np.int64)
+            out[f"{tag}_eval_len"] = np.asarray(ld.get_eval_len_list(), dtype=np.int64)
+            out[f"{tag}_eval_items"] = np.concatenate([np.asarray(x, dtype=np.int64) for x in ld.get_eval_items()])
+        out["row_strides"] = np.array([f"{k}={v}" for k, v in S.items()])
+        out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()])
+        path = os.path.join(out_dir, "grcn_small.npz")
+        np.savez_compressed(path, **out)
+        print(f"wrote {path}: {os.path.getsize(path) / 1e6:.2f} MB, keys={len(out)}")
+    finally:
+        torch.Tensor.cuda = orig_cuda
+    for f in ("grcn_small.npz", "grcn_step0_small.npz"):
+        assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec")
+    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     _install_shims()
@@ -1072,6 +1280,9 @@ def main():
         return
     if args.only == "lgmrec":
         capture_lgmrec(args.out)
+        return
+    if args.only == "grcn":
+        capture_grcn(args.out)
         return
     if args.only == "mf":
         capture_mf(args.out)
