@@ -1,4 +1,6 @@
-"""Shared test helpers: fixture decoding, comparisons and the multi-process rendezvous."""
+"""Shared test helpers: fixture decoding, comparisons, the multi-process rendezvous, and the
+scaffolding of the per-model GPU tests (dataset directory, loaders, model, epoch loop, the
+checks against a reference run).  Plain functions: a model's test file passes in what is its own."""
 from __future__ import annotations
 
 import atexit
@@ -8,6 +10,8 @@ import tempfile
 
 import numpy as np
 import torch
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def store_path() -> str:
@@ -110,3 +114,152 @@ def canonical_topk_fast(scores: np.ndarray, k: int):
         idx[r] = cand[order]
         val[r] = sv[order]
     return val, idx
+
+
+# ------------------------------------------------- the per-model tests' scaffolding
+def dev(a, device, grad=False):
+    """A numpy array on `device` (None stays None), as a leaf that requires grad if asked."""
+    if a is None:
+        return None
+    t = torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    return t.requires_grad_(True) if grad else t
+
+
+def check_vs_f32(name, got, ref, tor):
+    """|got - ref| within max(1e-4 scale, 4 |torch f32 - ref|)."""
+    ref = np.asarray(ref)
+    got = np.asarray(got, dtype=np.float64).reshape(ref.shape)
+    tor = np.asarray(tor, dtype=np.float64).reshape(ref.shape)
+    scale = float(np.abs(ref).max())
+    terr = float(np.abs(tor - ref).max())
+    bound = max(1e-4 * scale, 4 * terr)
+    err = float(np.abs(got - ref).max())
+    print(f"  {name}: err {err:.3e}, scale {scale:.3e}, torch f32 err {terr:.3e}, bound {bound:.3e}")
+    assert np.all(np.isfinite(got)), name
+    assert err <= bound, name
+
+
+def take_first(c):
+    """The first value of every hyper-parameter a Config lists several of; returns `c`."""
+    for k in c["hyper_parameters"]:
+        if isinstance(c[k], list):
+            c[k] = c[k][0]
+    return c
+
+
+def write_dataset(tmp_path, v_feat, t_feat):
+    """tmp_path/data/baby with the small interaction file and the feature tables given (None: no
+    file); returns the `data_path` of a Config."""
+    d = tmp_path / "data" / "baby"
+    d.mkdir(parents=True, exist_ok=True)
+    shutil.copy(os.path.join(GOLD, "gold_small.inter"), d / "baby.inter")
+    if v_feat is not None:
+        np.save(d / "image_feat_raw.npy", v_feat)
+    if t_feat is not None:
+        np.save(d / "text_feat_raw.npy", t_feat)
+    return str(tmp_path / "data") + "/"
+
+
+def loaders(model_name, tmp_path, cfg):
+    """(config, train, valid, test loaders) on write_dataset's directory: batches of 512, evaluation
+    batches of 256, the host sampler; `cfg` holds the model's own keys and overrides these."""
+    from rsx.config import Config
+    from rsx.data import EvalDataLoader, RecDataset, TrainDataLoader
+
+    common = dict(data_path=str(tmp_path / "data") + "/", train_batch_size=512, eval_batch_size=256, rsx_sampler="host")
+    c = take_first(Config(model_name, "baby", {**common, **cfg}))
+    ds = RecDataset(c)
+    tr, va, te = ds.split()
+    for s in (ds, tr, va, te):
+        str(s)
+    train = TrainDataLoader(c, tr, batch_size=512, shuffle=True)
+    valid = EvalDataLoader(c, va, additional_dataset=tr, batch_size=256)
+    test = EvalDataLoader(c, te, additional_dataset=tr, batch_size=256)
+    return c, train, valid, test
+
+
+def make_model(name, c, train):
+    from rsx.utils import get_model, init_seed
+
+    init_seed(c["seed"])
+    train.pretrain_setup()
+    return get_model(name)(c, train)
+
+
+def record_batches(train):
+    """Wraps the loader's batch source; returns the list every batch it hands out is appended to."""
+    rec, orig = [], train._next_batch_data
+
+    def wrapped():
+        b = orig()
+        rec.append(b.cpu().clone())
+        return b
+
+    train._next_batch_data = wrapped
+    return rec
+
+
+def train_epochs(t, m, train, epochs, after_pre_epoch=None, after_epoch=None):
+    """The Trainer's epochs as quick_start drives them, each loss a finite float; the hooks take
+    the epoch's number.  Returns the losses, the device idle."""
+    losses = []
+    for epoch in range(epochs):
+        m.cur_epoch = epoch
+        m.pre_epoch_processing()
+        if after_pre_epoch is not None:
+            after_pre_epoch(epoch)
+        loss, _ = t._train_epoch(train, epoch)
+        assert not torch.is_tensor(loss) and np.isfinite(loss)
+        losses.append(loss)
+        if after_epoch is not None:
+            after_epoch(epoch)
+        t.lr_scheduler.step()
+        t._epoch_for_lr += 1
+    torch.cuda.synchronize()
+    return losses
+
+
+def check_params(m, z, prefix, rel):
+    """Every parameter within rel of its scale of the fixture's z[prefix + name]."""
+    for n, p in m.named_parameters():
+        w = z[prefix + n]
+        scale = float(np.abs(w).max())
+        err = float(np.abs(p.detach().cpu().numpy() - w).max())
+        print(f"  {n}: err / scale {err / scale:.2e} (bound {rel:g})")
+        assert err <= rel * scale, n
+
+
+def check_eval(t, m, z, loaders, tag_prefix="epoch1_"):
+    """Per (split, loader): the metrics within 1e-4 of the fixture's, the evaluated users its own,
+    the top-50 equal modulo ties."""
+    for split, loader in loaders:
+        tag = tag_prefix + split
+        res = t.evaluate(loader)
+        ref = metric_dict(z, tag)
+        assert res.keys() == ref.keys()
+        for k in ref:
+            assert abs(res[k] - ref[k]) <= 1e-4, (k, res[k], ref[k])
+        assert np.array_equal(loader.eval_u.cpu().numpy(), z[tag + "_users"])
+        _, idx = m.full_sort_topk([loader.eval_u, None], 50, loader)
+        scores = m.full_sort_predict([loader.eval_u, None]).cpu().numpy()
+        assert topk_equal_modulo_ties(idx.cpu().numpy(), z[tag + "_topk_idx"].astype(np.int64), scores) == 0
+
+
+def assert_same_run(a, b, la, lb):
+    """Two runs bit for bit: equal losses, torch.equal parameters."""
+    assert la == lb
+    for (n, p), q in zip(a.named_parameters(), b.parameters()):
+        assert torch.equal(p, q), n
+
+
+def quick_start_case(model, tmp_path, v_feat, t_feat, overrides):
+    """`main.py -m <model> -d baby` from tmp_path on write_dataset's directory; quick_start's result."""
+    from rsx.quick_start import quick_start
+
+    cfg = {"data_path": write_dataset(tmp_path, v_feat, t_feat), "train_batch_size": 512, **overrides}
+    cwd = os.getcwd()
+    os.chdir(tmp_path)
+    try:
+        return quick_start(model, "baby", cfg, log=False)
+    finally:
+        os.chdir(cwd)

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import coo_sorted, csr_to_sorted, metric_dict, params
+from helpers import coo_sorted, csr_to_sorted, metric_dict, params, take_first
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -30,9 +30,7 @@ def _setup(tmp_path, model, extra):
     cfg.update(extra)
     c = Config(model, "baby", cfg)
     assert c["device"].type == "cpu"
-    for k in c["hyper_parameters"]:
-        if isinstance(c[k], list):
-            c[k] = c[k][0]
+    take_first(c)
     ds = RecDataset(c)
     tr, va, te = ds.split()
     for x in (ds, tr, va, te):

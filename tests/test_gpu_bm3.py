@@ -7,28 +7,21 @@ capture, and the entry points.
 The repeated rows' gradients are accumulated with f32 atomics, so there
 is no run-to-run bit-equality test of the backward; the forward is deterministic and is
 checked to be.  Observed figures are printed before every assertion (run with -s)."""
-import os
-import shutil
-
 import numpy as np
 import pytest
 import torch
 
 import bm3_ref as R
-from helpers import metric_dict
+from helpers import (dev, loaders, make_model, metric_dict, quick_start_case, record_batches, train_epochs,
+                     write_dataset)
 
 pytestmark = pytest.mark.gpu
 
-GOLD = R.GOLD
 U24 = 2.0 ** -24
 NU, NI = 11, 7  # every row repeats many times in a batch
 REG, CL = 0.1, 2.0
 PAIRS = (("user", "item", 1.0), ("item", "user", 1.0), ("text", "item", CL), ("image", "item", CL),
          ("text", "text", CL), ("image", "image", CL))
-
-
-def _dev(a, cuda="cuda"):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
 
 
 def _inputs(d, B, has_t, has_v, p, seed, nu=NU, ni=NI, zero_row=True):
@@ -53,9 +46,9 @@ def _run(cuda, c, masks=True, seed=7, backward=True):
     """(out [8], dict of gradients) of the kernels on the inputs `c`."""
     from rsx import bm3
 
-    t = {k: _dev(c[k], cuda) for k in ("E", "H", "T", "V", "P", "pb", "users", "items")}
+    t = {k: dev(c[k], cuda) for k in ("E", "H", "T", "V", "P", "pb", "users", "items")}
     d, B = c["E"].shape[1], len(c["users"])
-    m = {s: _dev(R.pack_keep(k).view(np.int32), cuda) for s, k in c["keep"].items()} if masks else None
+    m = {s: dev(R.pack_keep(k).view(np.int32), cuda) for s, k in c["keep"].items()} if masks else None
     ws = bm3.workspace(B, d, cuda)
     sd = torch.tensor([seed], dtype=torch.int64, device=cuda)
     a = bm3.bm3_args(t["E"], t["H"], t["T"], t["V"], t["P"], t["pb"], t["users"], t["items"], c["nu"], REG, CL,
@@ -259,10 +252,10 @@ def test_hashed_dropout(cuda):
     E = (rng.standard_normal((2 * n, d)) + 3.0).astype(np.float32)  # no zeros
     E[n:] = E[:n]  # the four tables hold the same values: targets differ by their masks only
     H = np.zeros((n, d), np.float32)
-    t = dict(E=_dev(E, cuda), H=_dev(H, cuda), T=_dev(E[n:], cuda), V=_dev(E[n:], cuda),
+    t = dict(E=dev(E, cuda), H=dev(H, cuda), T=dev(E[n:], cuda), V=dev(E[n:], cuda),
              P=torch.eye(d, device=cuda), pb=torch.zeros(d, device=cuda))
     idx = np.concatenate([np.arange(n), [5]]).astype(np.int64)  # row 5 occurs twice
-    users = items = _dev(idx, cuda)
+    users = items = dev(idx, cuda)
     B = idx.size
     ws = bm3.workspace(B, d, cuda)
     outs = []
@@ -293,39 +286,14 @@ def test_hashed_dropout(cuda):
 
 # ------------------------------------------------------------------ the model on the fixture data
 def _setup(tmp_path, extra):
-    from rsx.config import Config
-    from rsx.data import EvalDataLoader, RecDataset, TrainDataLoader
-
     z = R.load_fixture("small")
-    d = tmp_path / "data" / "baby"
-    d.mkdir(parents=True, exist_ok=True)
-    shutil.copy(os.path.join(GOLD, "gold_small.inter"), d / "baby.inter")
-    np.save(d / "image_feat_raw.npy", z["v_feat"])
-    np.save(d / "text_feat_raw.npy", z["t_feat"])
-    cfg = dict(data_path=str(tmp_path / "data") + "/", train_batch_size=512, eval_batch_size=256, rsx_sampler="host",
-               n_layers=1, dropout=0.0, reg_weight=0.1)
-    cfg.update(extra)
-    c = Config("BM3", "baby", cfg)
-    for k in c["hyper_parameters"]:
-        if isinstance(c[k], list):
-            c[k] = c[k][0]
-    ds = RecDataset(c)
-    tr, va, te = ds.split()
-    for x in (ds, tr, va, te):
-        str(x)
-    train = TrainDataLoader(c, tr, batch_size=512, shuffle=True)
-    valid = EvalDataLoader(c, va, additional_dataset=tr, batch_size=256)
-    test = EvalDataLoader(c, te, additional_dataset=tr, batch_size=256)
-    return c, train, valid, test
+    write_dataset(tmp_path, z["v_feat"], z["t_feat"])
+    return loaders("BM3", tmp_path, {"n_layers": 1, "dropout": 0.0, "reg_weight": 0.1, **extra})
 
 
 def _model(tmp_path, extra=None):
-    from rsx.utils import get_model, init_seed
-
     c, train, valid, test = _setup(tmp_path, extra or {})
-    init_seed(c["seed"])
-    train.pretrain_setup()
-    return get_model("BM3")(c, train), c, train, valid, test
+    return make_model("BM3", c, train), c, train, valid, test
 
 
 def _named(m):
@@ -352,9 +320,9 @@ def test_init_graph_and_first_step_vs_reference(cuda, tmp_path):
     assert np.array_equal(rows, z["adj_idx"][0][order]) and np.array_equal(A.col.cpu().numpy(), z["adj_idx"][1][order])
     assert np.array_equal(A.val.cpu().numpy().view(np.int32), z["adj_val"][order].view(np.int32))
     # the first step with the masks torch drew
-    masks = {s: _dev(z["keep_" + s].view(np.int32), cuda) for s in R.STREAMS}
+    masks = {s: dev(z["keep_" + s].view(np.int32), cuda) for s in R.STREAMS}
     m.train()
-    loss = m.calculate_loss(_dev(z["pairs"].astype(np.int64), cuda), keep_masks=masks)
+    loss = m.calculate_loss(dev(z["pairs"].astype(np.int64), cuda), keep_masks=masks)
     loss.backward()
     want = float(z["step0_loss"])
     print(f"loss {loss.item():.8f} vs reference {want:.8f} (rel {abs(loss.item() - want) / want:.2e})")
@@ -376,27 +344,8 @@ def _train(tmp_path, extra, epochs, record=False):
     t = Trainer(c, m)
     assert not t.fused and type(t.optimizer).__name__ == "RsxAdam"
     assert len(t.optimizer.param_groups[0]["params"]) == len(R.NAMES)  # RsxAdam steps every parameter
-    rec = []
-    if record:
-        orig = train._next_batch_data
-
-        def wrapped():
-            b = orig()
-            rec.append(b.cpu().clone())
-            return b
-
-        train._next_batch_data = wrapped
-    losses = []
-    for epoch in range(epochs):
-        m.cur_epoch = epoch
-        m.pre_epoch_processing()
-        loss, _ = t._train_epoch(train, epoch)
-        assert not torch.is_tensor(loss) and np.isfinite(loss)
-        losses.append(loss)
-        t.lr_scheduler.step()
-        t._epoch_for_lr += 1
-    torch.cuda.synchronize()
-    return m, t, valid, test, rec, losses
+    rec = record_batches(train) if record else []
+    return m, t, valid, test, rec, train_epochs(t, m, train, epochs)
 
 
 def test_trainer_vs_reference(cuda, tmp_path):
@@ -463,8 +412,8 @@ def test_captured_step_replays(cuda, tmp_path):
     batch after a captured full one, and with dropout 0.3 two replays of one batch giving
     different losses: the seed advances on the device."""
     z = R.load_fixture("small")
-    full = _dev(R.epoch_pairs(z, 0)[0], cuda)
-    short = _dev(R.epoch_pairs(z, 0)[-1], cuda)
+    full = dev(R.epoch_pairs(z, 0)[0], cuda)
+    short = dev(R.epoch_pairs(z, 0)[-1], cuda)
     seq = [full, full, full, full, short, short, short]
     a, la, ta = _steps(tmp_path, "graph", 0.0, seq, True)
     b, lb, tb = _steps(tmp_path, "eager", 0.0, seq, False)
@@ -485,21 +434,9 @@ def test_captured_step_replays(cuda, tmp_path):
 
 # ------------------------------------------------------------------ entry points
 def test_quick_start(cuda, tmp_path):
-    from rsx.quick_start import quick_start
-
     z = R.load_fixture("small")
-    d = tmp_path / "data" / "baby"
-    d.mkdir(parents=True)
-    shutil.copy(os.path.join(GOLD, "gold_small.inter"), d / "baby.inter")
-    np.save(d / "image_feat_raw.npy", z["v_feat"])
-    np.save(d / "text_feat_raw.npy", z["t_feat"])
-    cwd = os.getcwd()
-    os.chdir(tmp_path)
-    try:
-        res = quick_start("BM3", "baby", {"data_path": str(tmp_path / "data") + "/", "epochs": 1, "n_layers": [1],
-                                          "reg_weight": [0.1], "dropout": [0.3], "train_batch_size": 512}, log=False)
-    finally:
-        os.chdir(cwd)
+    res = quick_start_case("BM3", tmp_path, z["v_feat"], z["t_feat"],
+                           {"epochs": 1, "n_layers": [1], "reg_weight": [0.1], "dropout": [0.3]})
     assert len(res) == 1 and "recall@20" in res[0][1]
     assert all(np.isfinite(v) for v in res[0][1].values())
 

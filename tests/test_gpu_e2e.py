@@ -15,7 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import metric_dict, params
+from helpers import metric_dict, params, take_first
 
 pytestmark = pytest.mark.gpu
 
@@ -33,9 +33,7 @@ def _setup(tmp_path, model, extra):
                rsx_sampler="host", is_multimodal_model=False)
     cfg.update(extra)
     c = Config(model, "baby", cfg)
-    for k in c["hyper_parameters"]:
-        if isinstance(c[k], list):
-            c[k] = c[k][0]
+    take_first(c)
     ds = RecDataset(c)
     tr, va, te = ds.split()
     for x in (ds, tr, va, te):

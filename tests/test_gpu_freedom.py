@@ -12,38 +12,15 @@ float atomics), and the captured graph step equals the eager one bit for bit.
 Model bounds: the CPU tests' (tests/test_freedom_cpu.py) for the first step, the project's
 end-to-end bounds for two epochs (parameters 5e-5 of scale, metrics 1e-4, top-50 equal
 modulo the recorded ties)."""
-import os
-import shutil
-
 import numpy as np
 import pytest
 import torch
 
 import freedom_ref as R
-from helpers import coo_sorted, csr_to_sorted, metric_dict, topk_equal_modulo_ties
+from helpers import (assert_same_run, check_eval, check_params, check_vs_f32, coo_sorted, csr_to_sorted, dev, loaders,
+                     make_model, quick_start_case, record_batches, train_epochs, write_dataset)
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev(a, cuda, grad=False):
-    if a is None:
-        return None
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-    return t.requires_grad_(True) if grad else t
-
-
-def _check(name, got, ref, tor):
-    """|got - ref| within max(1e-4 scale, 4 |torch f32 - ref|)."""
-    ref = np.asarray(ref)
-    got = np.asarray(got, dtype=np.float64).reshape(ref.shape)
-    tor = np.asarray(tor, dtype=np.float64).reshape(ref.shape)
-    scale = float(np.abs(ref).max())
-    terr = float(np.abs(tor - ref).max())
-    bound = max(1e-4 * scale, 4 * terr)
-    err = float(np.abs(got - ref).max())
-    print(f"  {name}: err {err:.3e}, scale {scale:.3e}, torch f32 err {terr:.3e}, bound {bound:.3e}")
-    assert np.all(np.isfinite(got)), name
-    assert err <= bound, name
 
 
 # ------------------------------------------------------------------ the loss kernel
@@ -88,9 +65,9 @@ def _run_loss(x, nu, reg, H, T, V, cuda):
 
     d, B = x["E"].shape[1], x["trip"].shape[1]
     ws = F.workspace(B, d, cuda)
-    E, Hd, Td, Vd = _dev(x["E"], cuda, True), _dev(H, cuda, True), _dev(T, cuda, True), _dev(V, cuda, True)
+    E, Hd, Td, Vd = dev(x["E"], cuda, True), dev(H, cuda, True), dev(T, cuda, True), dev(V, cuda, True)
     keep = {}
-    loss = F._FreedomLoss.apply((nu, reg, ws, keep), _dev(x["trip"], cuda), E, Hd, Td, Vd, None, None)
+    loss = F._FreedomLoss.apply((nu, reg, ws, keep), dev(x["trip"], cuda), E, Hd, Td, Vd, None, None)
     loss.backward()
     c = lambda t: None if t is None else t.detach().cpu().numpy()  # noqa: E731
     out = c(keep["terms"])
@@ -128,7 +105,7 @@ def test_loss_kernel_vs_restatement(cuda, d, B, nu, ni):
                     if ref[k] is None:
                         assert got[k] is None, name
                         continue
-                    _check(name, got[k], ref[k], tor[k])
+                    check_vs_f32(name, got[k], ref[k], tor[k])
                 # rows off the batch are exact zeros
                 off_u = np.setdiff1d(np.arange(nu), trip[0])
                 off_i = np.setdiff1d(np.arange(ni), np.concatenate([trip[1], trip[2]]))
@@ -195,42 +172,16 @@ def test_item_graph_device_vs_host(cuda):
 
 
 def _setup(tmp_path, extra=None, feats=None):
-    from rsx.config import Config
-    from rsx.data import EvalDataLoader, RecDataset, TrainDataLoader
-
     z = R.load_fixture()
-    d = tmp_path / "data" / "baby"
-    d.mkdir(parents=True)
-    shutil.copy(os.path.join(R.GOLD, "gold_small.inter"), d / "baby.inter")
-    v, t = feats if feats is not None else (z["v_feat"], z["t_feat"])
-    if v is not None:
-        np.save(d / "image_feat_raw.npy", v)
-    if t is not None:
-        np.save(d / "text_feat_raw.npy", t)
-    cfg = dict(data_path=str(tmp_path / "data") + "/", train_batch_size=512, eval_batch_size=256, rsx_sampler="host",
-               rsx_edge_dropout="host", rsx_knn="host", is_multimodal_model=True, dropout=[R.HPARAMS["dropout"]],
+    write_dataset(tmp_path, *(feats if feats is not None else (z["v_feat"], z["t_feat"])))
+    cfg = dict(rsx_edge_dropout="host", rsx_knn="host", is_multimodal_model=True, dropout=[R.HPARAMS["dropout"]],
                reg_weight=[R.HPARAMS["reg_weight"]])
     cfg.update(extra or {})
-    c = Config("FREEDOM", "baby", cfg)
-    for k in c["hyper_parameters"]:
-        if isinstance(c[k], list):
-            c[k] = c[k][0]
-    ds = RecDataset(c)
-    tr, va, te = ds.split()
-    for s in (ds, tr, va, te):
-        str(s)
-    train = TrainDataLoader(c, tr, batch_size=512, shuffle=True)
-    valid = EvalDataLoader(c, va, additional_dataset=tr, batch_size=256)
-    test = EvalDataLoader(c, te, additional_dataset=tr, batch_size=256)
-    return z, c, train, valid, test
+    return (z,) + loaders("FREEDOM", tmp_path, cfg)
 
 
 def _model(c, train):
-    from rsx.utils import get_model, init_seed
-
-    init_seed(c["seed"])
-    train.pretrain_setup()
-    return get_model("FREEDOM")(c, train)
+    return make_model("FREEDOM", c, train)
 
 
 def _csr_sorted(A):
@@ -302,7 +253,7 @@ def test_freedom_first_step(cuda, tmp_path):
     m.train()
     m.build_epoch_graph(z["e0_keep_ids"])
     opt = torch.optim.Adam(m.parameters(), lr=c["learning_rate"])
-    trip = _dev(z["step0_triplets"].astype(np.int64), cuda)
+    trip = dev(z["step0_triplets"].astype(np.int64), cuda)
     loss = m.calculate_loss(trip)
     loss.backward()
     want = float(z["step0_loss"])
@@ -321,12 +272,7 @@ def test_freedom_first_step(cuda, tmp_path):
         else:
             np.testing.assert_allclose(mine[n], w, rtol=1e-3, atol=1e-5 * scale, err_msg=n)
     opt.step()
-    for n, p in m.named_parameters():
-        got, want = p.detach().cpu().numpy(), z["step0_param." + n]
-        scale = float(np.abs(want).max())
-        err = float(np.abs(got - want).max())
-        print(f"  param {n}: err {err:.3e}, scale {scale:.3e}, err / scale {err / scale:.2e} (bound 1e-5)")
-        assert err <= 1e-5 * scale, n
+    check_params(m, z, "step0_param.", 1e-5)
     # Adam's state advanced on the biases too (a zero gradient, not an absent one)
     assert all(len(opt.state[p]) for p in m.parameters())
 
@@ -345,7 +291,7 @@ def _steps(tmp_path, tag, z, cuda, graph):
         t.reset_graph_step()
         trip = z[f"epoch{ep}_triplets"].astype(np.int64)
         for k in range(3):
-            losses.append(t.train_step(_dev(trip[:, 512 * k: 512 * (k + 1)], cuda), k)[1])
+            losses.append(t.train_step(dev(trip[:, 512 * k: 512 * (k + 1)], cuda), k)[1])
         replays.append(t._graph.replays if t._graph is not None else 0)
     torch.cuda.synchronize()
     return m, [float(x) for x in losses], replays
@@ -358,9 +304,7 @@ def test_freedom_captured_step_equals_eager(cuda, tmp_path):
     # per epoch: batch 0 eager, batch 1 captured and replayed, batch 2 a replay; the second
     # epoch captures again on its own graph
     assert ra[0] >= 1 and ra[1] >= 1 and rb == [0, 0]
-    assert la == lb
-    for (n, p), q in zip(a.named_parameters(), b.parameters()):
-        assert torch.equal(p, q), n
+    assert_same_run(a, b, la, lb)
 
 
 def test_freedom_trainer_vs_reference(cuda, tmp_path):
@@ -370,14 +314,7 @@ def test_freedom_trainer_vs_reference(cuda, tmp_path):
     m = _model(c, train)
     t = Trainer(c, m)
     assert not t.fused and type(t.optimizer).__name__ == "RsxAdam"
-    rec, orig = [], train._next_batch_data
-
-    def wrapped():
-        b = orig()
-        rec.append(b.cpu().clone())
-        return b
-
-    train._next_batch_data = wrapped
+    rec = record_batches(train)
     kept, build = [], m.build_epoch_graph
 
     def recording(ids):
@@ -385,39 +322,17 @@ def test_freedom_trainer_vs_reference(cuda, tmp_path):
         return build(ids)
 
     m.build_epoch_graph = recording
-    losses = []
-    for epoch in range(2):
-        m.cur_epoch = epoch
-        m.pre_epoch_processing()
-        # the draw first: it pins the order the RNG streams are consumed in
+
+    def the_draw_first(epoch):  # it pins the order the RNG streams are consumed in
         assert len(kept) == epoch + 1 and np.array_equal(kept[epoch], z[f"e{epoch}_keep_ids"]), epoch
-        loss, _ = t._train_epoch(train, epoch)
-        assert not torch.is_tensor(loss) and np.isfinite(loss)
-        losses.append(loss)
-        t.lr_scheduler.step()
-        t._epoch_for_lr += 1
-    torch.cuda.synchronize()
+
+    losses = train_epochs(t, m, train, 2, after_pre_epoch=the_draw_first)
     want = np.concatenate([z[f"epoch{e}_triplets"] for e in range(2)], axis=1).astype(np.int64)
     assert np.array_equal(torch.cat(rec, dim=1).numpy(), want)  # the recorded triplets
     assert t._graph is not None and t._graph.replays > 0
     print(f"epoch losses {losses} vs reference {z['epoch_losses']}")
-    for n, p in m.named_parameters():
-        w = z["epoch1_param." + n]
-        scale = float(np.abs(w).max())
-        err = float(np.abs(p.detach().cpu().numpy() - w).max())
-        print(f"  {n}: err / scale {err / scale:.2e} (bound 5e-5)")
-        assert err <= 5e-5 * scale, n
-    for split, loader in (("valid", valid), ("test", test)):
-        tag = f"epoch1_{split}"
-        res = t.evaluate(loader)
-        ref = metric_dict(z, tag)
-        assert res.keys() == ref.keys()
-        for k in ref:
-            assert abs(res[k] - ref[k]) <= 1e-4, (k, res[k], ref[k])
-        assert np.array_equal(loader.eval_u.cpu().numpy(), z[tag + "_users"])
-        _, idx = m.full_sort_topk([loader.eval_u, None], 50, loader)
-        scores = m.full_sort_predict([loader.eval_u, None]).cpu().numpy()
-        assert topk_equal_modulo_ties(idx.cpu().numpy(), z[tag + "_topk_idx"].astype(np.int64), scores) == 0
+    check_params(m, z, "epoch1_param.", 5e-5)
+    check_eval(t, m, z, (("valid", valid), ("test", test)))
     # training again invalidates the cached evaluation tables
     assert m._eval_cache is not None
     m.train()
@@ -461,7 +376,7 @@ def test_freedom_text_only_model(cuda, tmp_path):
     m.build_epoch_graph(z["e0_keep_ids"])
     trip = z["step0_triplets"].astype(np.int64)
     p = {n: q.detach().cpu().numpy() for n, q in m.named_parameters()}
-    loss = m.calculate_loss(_dev(trip, cuda))
+    loss = m.calculate_loss(dev(trip, cuda))
     loss.backward()
     ni = m.n_items
     r, cc, w = freedom_item_graph(None, torch.from_numpy(z["t_feat"]), R.KNN_K, R.IMAGE_WEIGHT, mode="host")
@@ -479,20 +394,8 @@ def test_freedom_quick_start(cuda, tmp_path):
     """`main.py -m FREEDOM -d <dataset>`'s path: trains an epoch (device edge dropout, device
     kNN: the defaults) and evaluates on a dataset directory with the .inter file and the
     feature files."""
-    from rsx.quick_start import quick_start
-
     z = R.load_fixture()
-    d = tmp_path / "data" / "baby"
-    d.mkdir(parents=True)
-    shutil.copy(os.path.join(R.GOLD, "gold_small.inter"), d / "baby.inter")
-    np.save(d / "image_feat_raw.npy", z["v_feat"])
-    np.save(d / "text_feat_raw.npy", z["t_feat"])
-    cwd = os.getcwd()
-    os.chdir(tmp_path)
-    try:
-        res = quick_start("FREEDOM", "baby", {"data_path": str(tmp_path / "data") + "/", "epochs": 1, "dropout": [0.8],
-                                              "reg_weight": [0.001], "train_batch_size": 512}, log=False)
-    finally:
-        os.chdir(cwd)
+    res = quick_start_case("FREEDOM", tmp_path, z["v_feat"], z["t_feat"],
+                           {"epochs": 1, "dropout": [0.8], "reg_weight": [0.001]})
     assert len(res) == 1 and "recall@20" in res[0][1]
     assert all(np.isfinite(v) for v in res[0][1].values())

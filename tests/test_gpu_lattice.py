@@ -17,38 +17,15 @@ Bounds.
 * Model: the first two steps' gradients rtol 1e-3, atol 1e-5 of the tensor's scale; two epochs
   5e-5 of the parameter's scale, metrics 1e-4, top-50 equal modulo the recorded ties.
 """
-import os
-import shutil
-
 import numpy as np
 import pytest
 import torch
 
 import lattice_ref as R
-from helpers import coo_sorted, csr_to_sorted, metric_dict, topk_equal_modulo_ties
+from helpers import (assert_same_run, check_eval, check_params, check_vs_f32, coo_sorted, csr_to_sorted, dev, loaders,
+                     make_model, quick_start_case, record_batches, train_epochs, write_dataset)
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev(a, cuda, grad=False):
-    if a is None:
-        return None
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-    return t.requires_grad_(True) if grad else t
-
-
-def _check(name, got, ref, tor):
-    """|got - ref| within max(1e-4 scale, 4 |torch f32 - ref|)."""
-    ref = np.asarray(ref)
-    got = np.asarray(got, dtype=np.float64).reshape(ref.shape)
-    tor = np.asarray(tor, dtype=np.float64).reshape(ref.shape)
-    scale = float(np.abs(ref).max())
-    terr = float(np.abs(tor - ref).max())
-    bound = max(1e-4 * scale, 4 * terr)
-    err = float(np.abs(got - ref).max())
-    print(f"  {name}: err {err:.3e}, scale {scale:.3e}, torch f32 err {terr:.3e}, bound {bound:.3e}")
-    assert np.all(np.isfinite(got)), name
-    assert err <= bound, name
 
 
 # ------------------------------------------------------------------ 1. the loss kernel
@@ -69,9 +46,9 @@ def _run_loss(x, nu, reg, bs, cuda):
 
     d, B = x["E"].shape[1], x["trip"].shape[1]
     ws = LT.workspace(B, d, cuda)
-    E, H = _dev(x["E"], cuda, True), _dev(x["H"], cuda, True)
+    E, H = dev(x["E"], cuda, True), dev(x["H"], cuda, True)
     keep = {}
-    loss = LT._LatticeLoss.apply((nu, reg, bs, ws, keep), _dev(x["trip"], cuda), E, H)
+    loss = LT._LatticeLoss.apply((nu, reg, bs, ws, keep), dev(x["trip"], cuda), E, H)
     loss.backward()
     out = keep["terms"].detach().cpu().numpy()
     assert out[0] == loss.item() or (np.isnan(out[0]) and np.isnan(loss.item()))
@@ -96,8 +73,8 @@ def test_loss_kernel_vs_restatement(cuda, d, B, nu, ni):
         for k, name in enumerate(("total", "mf", "emb")):
             print(f"  {name}: {got[0][k]:.8f} vs {ref[0][k]:.8f}")
             assert abs(got[0][k] - ref[0][k]) <= 1e-5 * abs(ref[0][k]), name
-        _check("gE", got[1], ref[1], tor[1])
-        _check("gH", got[2], ref[2], tor[2])
+        check_vs_f32("gE", got[1], ref[1], tor[1])
+        check_vs_f32("gH", got[2], ref[2], tor[2])
         off_u = np.setdiff1d(np.arange(nu), trip[0])
         off_i = np.setdiff1d(np.arange(ni), np.concatenate([trip[1], trip[2]]))
         assert not got[1][off_u].any() and not got[1][nu + off_i].any() and not got[2][off_i].any()
@@ -181,10 +158,10 @@ def _graph_case(N, k, M, L):
 def _device_graph(c, cuda):
     from rsx.lattice import ItemGraph
 
-    Fs = [_dev(F, cuda, True) for F in c["F"]]
-    mw = _dev(c["mw"], cuda, True)
-    g = ItemGraph(Fs, [_dev(i, cuda) for i in c["idx"]], [_dev(i, cuda) for i in c["oidx"]],
-                  [_dev(v, cuda) for v in c["oval"]], mw, c["lam"])
+    Fs = [dev(F, cuda, True) for F in c["F"]]
+    mw = dev(c["mw"], cuda, True)
+    g = ItemGraph(Fs, [dev(i, cuda) for i in c["idx"]], [dev(i, cuda) for i in c["oidx"]],
+                  [dev(v, cuda) for v in c["oval"]], mw, c["lam"])
     return g, Fs, mw
 
 
@@ -208,7 +185,7 @@ def test_graph_forward_and_propagation_vs_dense(cuda, N, k, M, L):
     te, tp = g.tedge.cpu().numpy().astype(np.int64), g.tptr.cpu().numpy()
     assert np.array_equal(te, np.argsort(col.reshape(-1), kind="stable"))
     assert np.array_equal(tp, np.concatenate([[0], np.cumsum(np.bincount(col.reshape(-1), minlength=N))]))
-    x, gr = _dev(c["h"], cuda), _dev(c["G"], cuda)
+    x, gr = dev(c["h"], cuda), dev(c["G"], cuda)
     y, yt = x, gr
     want, want_t = c["h"].astype(np.float64), c["G"].astype(np.float64)
     mag, mag_t = np.abs(want), np.abs(want_t)
@@ -242,9 +219,9 @@ def test_graph_backward_vs_autograd(cuda, N, k, M, L):
     runs = []
     for _ in range(2):
         g, Fs, mw = _device_graph(c, cuda)
-        h = _dev(c["h"], cuda, True)
+        h = dev(c["h"], cuda, True)
         H = _ItemProp.apply(h, g, L, True, mw, *Fs)
-        (H * _dev(c["G"], cuda)).sum().backward()
+        (H * dev(c["G"], cuda)).sum().backward()
         got = dict(h=h.grad.cpu().numpy(), **{f"F{m}": Fs[m].grad.cpu().numpy() for m in range(M)})
         if M == 2:
             got["mw"] = mw.grad.cpu().numpy()
@@ -271,43 +248,18 @@ def test_graph_backward_vs_autograd(cuda, N, k, M, L):
 
 # ------------------------------------------------------------------------- the model
 def _setup(tmp_path, extra=None, feats="both"):
-    from rsx.config import Config
-    from rsx.data import EvalDataLoader, RecDataset, TrainDataLoader
-
     z = R.load_fixture()
-    d = tmp_path / "data" / "baby"
-    d.mkdir(parents=True)
-    shutil.copy(os.path.join(R.GOLD, "gold_small.inter"), d / "baby.inter")
-    if feats in ("both", "image", "narrow"):
-        np.save(d / "image_feat_raw.npy", z["v_feat"])
-    if feats in ("both", "text"):
-        np.save(d / "text_feat_raw.npy", z["t_feat"])
-    if feats == "narrow":  # a text table whose width is no multiple of 4
-        np.save(d / "text_feat_raw.npy", z["t_feat"][:, :6])
-    cfg = dict(data_path=str(tmp_path / "data") + "/", train_batch_size=512, eval_batch_size=256, rsx_sampler="host",
-               is_multimodal_model=True, reg_weight=[R.HPARAMS["reg_weight"]],
+    # narrow: a text table whose width is no multiple of 4
+    text = {"both": z["t_feat"], "text": z["t_feat"], "narrow": z["t_feat"][:, :6]}.get(feats)
+    write_dataset(tmp_path, z["v_feat"] if feats != "text" else None, text)
+    cfg = dict(is_multimodal_model=True, reg_weight=[R.HPARAMS["reg_weight"]],
                learning_rate=[R.HPARAMS["learning_rate"]])
     cfg.update(extra or {})
-    c = Config("LATTICE", "baby", cfg)
-    for k in c["hyper_parameters"]:
-        if isinstance(c[k], list):
-            c[k] = c[k][0]
-    ds = RecDataset(c)
-    tr, va, te = ds.split()
-    for s in (ds, tr, va, te):
-        str(s)
-    train = TrainDataLoader(c, tr, batch_size=512, shuffle=True)
-    valid = EvalDataLoader(c, va, additional_dataset=tr, batch_size=256)
-    test = EvalDataLoader(c, te, additional_dataset=tr, batch_size=256)
-    return z, c, train, valid, test
+    return (z,) + loaders("LATTICE", tmp_path, cfg)
 
 
 def _model(c, train):
-    from rsx.utils import get_model, init_seed
-
-    init_seed(c["seed"])
-    train.pretrain_setup()
-    return get_model("LATTICE")(c, train)
+    return make_model("LATTICE", c, train)
 
 
 def _load_params(m, z, prefix):
@@ -383,7 +335,7 @@ def test_lattice_first_two_steps(cuda, tmp_path):
     for s in (0, 1):
         opt.zero_grad(set_to_none=True)
         assert m.graph_step_eager() == (s == 0)
-        loss = m.calculate_loss(_dev(trip[:, 512 * s: 512 * (s + 1)], cuda))
+        loss = m.calculate_loss(dev(trip[:, 512 * s: 512 * (s + 1)], cuda))
         loss.backward()
         want = float(z[f"step{s}_loss"])
         print(f"step {s}: loss {loss.item():.8f} vs reference {want:.8f}; words {m.last_terms.cpu().numpy()}")
@@ -399,10 +351,7 @@ def test_lattice_first_two_steps(cuda, tmp_path):
             print(f"  step {s} grad {n}: err {np.abs(g - w).max():.3e}, scale {scale:.3e}")
             np.testing.assert_allclose(g, w, rtol=1e-3, atol=1e-5 * scale, err_msg=f"step {s} {n}")
         opt.step()
-        for n, p in m.named_parameters():
-            got, want = p.detach().cpu().numpy(), z[f"step{s}_param.{n}"]
-            scale = float(np.abs(want).max())
-            assert np.abs(got - want).max() <= 1e-5 * scale, (s, n)
+        check_params(m, z, f"step{s}_param.", 1e-5)
     # Adam skipped the graph-only parameters on the steady batch: one step taken, as the reference's
     for n, p in m.named_parameters():
         assert int(opt.state[p]["step"].item()) == (1 if n in R.GRAPH_ONLY else 2), n
@@ -423,7 +372,7 @@ def _steps(tmp_path, tag, z, cuda, graph):
         dropped.append(t._graph is None)
         trip = z[f"epoch{ep}_triplets"].astype(np.int64)
         for k in range(4):
-            losses.append(t.train_step(_dev(trip[:, 512 * k: 512 * (k + 1)], cuda), k)[1])
+            losses.append(t.train_step(dev(trip[:, 512 * k: 512 * (k + 1)], cuda), k)[1])
         replays.append(t._graph.replays if t._graph is not None else 0)
     torch.cuda.synchronize()
     return m, [float(x) for x in losses], replays, dropped
@@ -436,9 +385,7 @@ def test_lattice_captured_step_equals_eager(cuda, tmp_path):
     # per epoch: batch 0 (the build) eager, batch 1 eager (the first steady one), batch 2 captured
     # and replayed, batch 3 a replay; the epoch boundary drops the capture
     assert ra == [2, 2] and rb == [0, 0] and da == [True, True]
-    assert la == lb
-    for (n, p), q in zip(a.named_parameters(), b.parameters()):
-        assert torch.equal(p, q), n
+    assert_same_run(a, b, la, lb)
 
 
 def test_lattice_trainer_vs_reference(cuda, tmp_path):
@@ -448,49 +395,21 @@ def test_lattice_trainer_vs_reference(cuda, tmp_path):
     m = _model(c, train)
     t = Trainer(c, m)
     assert not t.fused and type(t.optimizer).__name__ == "RsxAdam"
-    rec, orig = [], train._next_batch_data
+    rec = record_batches(train)
 
-    def wrapped():
-        b = orig()
-        rec.append(b.cpu().clone())
-        return b
-
-    train._next_batch_data = wrapped
-    losses = []
-    for epoch in range(2):
-        m.cur_epoch = epoch
-        m.pre_epoch_processing()
-        loss, _ = t._train_epoch(train, epoch)
-        assert not torch.is_tensor(loss) and np.isfinite(loss)
-        losses.append(loss)
-        for mod, idx in zip(m.mods, m.item_graph.idx):  # the epoch's build
+    def epochs_build(epoch):  # the neighbours the epoch's build chose
+        for mod, idx in zip(m.mods, m.item_graph.idx):
             bad, _ = _same_sets(idx.cpu().numpy(), z[f"build{epoch}_{mod}_idx"], z[f"build{epoch}_{mod}_gap"])
             assert bad == 0, (epoch, mod)
-        t.lr_scheduler.step()
-        t._epoch_for_lr += 1
-    torch.cuda.synchronize()
+
+    losses = train_epochs(t, m, train, 2, after_epoch=epochs_build)
     want = np.concatenate([z[f"epoch{e}_triplets"] for e in range(2)], axis=1).astype(np.int64)
     assert np.array_equal(torch.cat(rec, dim=1).numpy(), want)  # the recorded triplets
     assert t._graph is not None and t._graph.replays > 0
     print(f"epoch losses {losses} vs reference {z['epoch_losses']}")
     np.testing.assert_allclose(losses, z["epoch_losses"], rtol=1e-5)
-    for n, p in m.named_parameters():
-        w = z["epoch1_param." + n]
-        scale = float(np.abs(w).max())
-        err = float(np.abs(p.detach().cpu().numpy() - w).max())
-        print(f"  {n}: err / scale {err / scale:.2e} (bound 5e-5)")
-        assert err <= 5e-5 * scale, n
-    for split, loader in (("valid", valid), ("test", test)):
-        tag = f"epoch1_{split}"
-        res = t.evaluate(loader)
-        ref = metric_dict(z, tag)
-        assert res.keys() == ref.keys()
-        for k in ref:
-            assert abs(res[k] - ref[k]) <= 1e-4, (k, res[k], ref[k])
-        assert np.array_equal(loader.eval_u.cpu().numpy(), z[tag + "_users"])
-        _, idx = m.full_sort_topk([loader.eval_u, None], 50, loader)
-        scores = m.full_sort_predict([loader.eval_u, None]).cpu().numpy()
-        assert topk_equal_modulo_ties(idx.cpu().numpy(), z[tag + "_topk_idx"].astype(np.int64), scores) == 0
+    check_params(m, z, "epoch1_param.", 5e-5)
+    check_eval(t, m, z, (("valid", valid), ("test", test)))
     # the evaluation tables are cached until train() is called
     assert m._eval_cache is not None
     m.train()
@@ -505,7 +424,7 @@ def _one_step_vs_restatement(m, z, cuda, mods, cf_model):
     want, g = ref.loss_backward(trip)
     m.train()
     m.pre_epoch_processing()
-    loss = m.calculate_loss(_dev(trip, cuda))
+    loss = m.calculate_loss(dev(trip, cuda))
     loss.backward()
     print(f"loss {loss.item():.8f} vs restatement {want:.8f}")
     assert abs(loss.item() - want) <= 1e-5 * abs(want)
@@ -557,21 +476,8 @@ def test_lattice_unsupported_configurations_raise(cuda, tmp_path, what):
 def test_lattice_quick_start(cuda, tmp_path):
     """`main.py -m LATTICE -d <dataset>`'s path: trains an epoch and evaluates on a dataset
     directory with the .inter file and the feature files."""
-    from rsx.quick_start import quick_start
-
     z = R.load_fixture()
-    d = tmp_path / "data" / "baby"
-    d.mkdir(parents=True)
-    shutil.copy(os.path.join(R.GOLD, "gold_small.inter"), d / "baby.inter")
-    np.save(d / "image_feat_raw.npy", z["v_feat"])
-    np.save(d / "text_feat_raw.npy", z["t_feat"])
-    cwd = os.getcwd()
-    os.chdir(tmp_path)
-    try:
-        res = quick_start("LATTICE", "baby", {"data_path": str(tmp_path / "data") + "/", "epochs": 1,
-                                              "reg_weight": [0.001], "learning_rate": [0.001],
-                                              "train_batch_size": 512}, log=False)
-    finally:
-        os.chdir(cwd)
+    res = quick_start_case("LATTICE", tmp_path, z["v_feat"], z["t_feat"],
+                           {"epochs": 1, "reg_weight": [0.001], "learning_rate": [0.001]})
     assert len(res) == 1 and "recall@20" in res[0][1]
     assert all(np.isfinite(v) for v in res[0][1].values())

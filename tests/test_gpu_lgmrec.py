@@ -10,38 +10,16 @@ Bounds (tests/test_gpu_lattice.py's rules).
 * Assignment forward: 1e-6 absolute.  Hypergraph forward: 1e-5 of sum |terms| per element.
 * Model: see the tests.
 """
-import os
-import shutil
-
 import numpy as np
 import pytest
 import torch
 
 import lgmrec_ref as R
+from helpers import (assert_same_run, check_vs_f32, coo_sorted, csr_to_sorted, dev, loaders, make_model,
+                     topk_equal_modulo_ties, write_dataset)
 
 pytestmark = pytest.mark.gpu
 TAU = float(np.float32(0.2))  # the float32 tau the kernels are handed
-
-
-def _dev(a, cuda, grad=False):
-    if a is None:
-        return None
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-    return t.requires_grad_(True) if grad else t
-
-
-def _check(name, got, ref, tor):
-    """|got - ref| within max(1e-4 scale, 4 |torch f32 - ref|)."""
-    ref = np.asarray(ref)
-    got = np.asarray(got, dtype=np.float64).reshape(ref.shape)
-    tor = np.asarray(tor, dtype=np.float64).reshape(ref.shape)
-    scale = float(np.abs(ref).max())
-    terr = float(np.abs(tor - ref).max())
-    bound = max(1e-4 * scale, 4 * terr)
-    err = float(np.abs(got - ref).max())
-    print(f"  {name}: err {err:.3e}, scale {scale:.3e}, torch f32 err {terr:.3e}, bound {bound:.3e}")
-    assert np.all(np.isfinite(got)), name
-    assert err <= bound, name
 
 
 def _check_word(name, got, ref, tor):
@@ -58,10 +36,10 @@ def _bits(a, b):
 def _run_ssl(T1, T2, idx, cuda):
     from rsx import lgmrec as LG
 
-    a = _dev(T1, cuda, True)
-    b = a if T2 is None else _dev(T2, cuda, True)
+    a = dev(T1, cuda, True)
+    b = a if T2 is None else dev(T2, cuda, True)
     ws = LG.ssl_workspace(T1.shape[0], idx.size, T1.shape[1], cuda)
-    loss = LG._Ssl.apply((TAU, ws), _dev(idx, cuda), a, b)
+    loss = LG._Ssl.apply((TAU, ws), dev(idx, cuda), a, b)
     loss.backward()
     return loss.item(), a.grad.cpu().numpy(), None if T2 is None else b.grad.cpu().numpy()
 
@@ -72,9 +50,9 @@ def _ssl_case(T1, T2, idx, cuda, tag):
     tor = R.ssl_grad(T1, T2, idx, TAU, dtype=torch.float32)
     got = _run_ssl(T1, T2, idx, cuda)
     _check_word("loss", got[0], ref[0], tor[0])
-    _check("gT1", got[1], ref[1], tor[1])
+    check_vs_f32("gT1", got[1], ref[1], tor[1])
     if T2 is not None:
-        _check("gT2", got[2], ref[2], tor[2])
+        check_vs_f32("gT2", got[2], ref[2], tor[2])
         off = np.setdiff1d(np.arange(T1.shape[0]), idx)  # rows of T1 the loss cannot reach
         assert not got[1][off].any()
     again = _run_ssl(T1, T2, idx, cuda)  # deterministic: a second call is bit-equal
@@ -135,9 +113,9 @@ def test_ssl_kernel_equal_rows_and_zero_row(cuda, same):
     idx = np.concatenate([rng.integers(0, N, 20), [3, 5, 7]]).astype(np.int64)
     got, ref, tor = _ssl_case(T1, T2, idx, cuda, f"equal rows, zero row, same={same}")
     rest = np.arange(N) != 7  # the other rows at their own scale
-    _check("gT1 off the zero row", got[1][rest], ref[1][rest], tor[1][rest])
+    check_vs_f32("gT1 off the zero row", got[1][rest], ref[1][rest], tor[1][rest])
     if not same:
-        _check("gT2 off the zero row", got[2][rest], ref[2][rest], tor[2][rest])
+        check_vs_f32("gT2 off the zero row", got[2][rest], ref[2][rest], tor[2][rest])
 
 
 def test_ssl_kernel_limits(cuda):
@@ -178,7 +156,7 @@ def test_assign_kernel_vs_restatement(cuda, n, H, keep_rate):
     dy = rng.standard_normal((n, H)).astype(np.float32)
     ref = R.assign_grad(x[:, :H], noise, keep, keep_rate, dy, TAU)
     tor = R.assign_grad(x[:, :H], noise, keep, keep_rate, dy, TAU, dtype=torch.float32)
-    xd, nd, kd = _dev(x, cuda), _dev(noise, cuda), _dev(R.pack_keep(keep).view(np.int32), cuda)
+    xd, nd, kd = dev(x, cuda), dev(noise, cuda), dev(R.pack_keep(keep).view(np.int32), cuda)
     y0 = torch.full((n, ld), -3.0, device=cuda)
     o0 = torch.full((n, ld), -4.0, device=cuda)
     y, out = LG.assign_fwd(xd, H, TAU, keep_rate, nd, kd, y=y0, out=o0)
@@ -190,8 +168,8 @@ def test_assign_kernel_vs_restatement(cuda, n, H, keep_rate):
     dyp = np.full((n, ld), np.nan, dtype=np.float32)  # the pad columns: never read
     dyp[:, :H] = dy
     dx0 = torch.full((n, ld), -5.0, device=cuda)
-    dx = LG.assign_bwd(xd, H, TAU, keep_rate, y, _dev(dyp, cuda), kd, dx=dx0)
-    _check("dx", dx[:, :H].cpu().numpy(), ref[2], tor[2])
+    dx = LG.assign_bwd(xd, H, TAU, keep_rate, y, dev(dyp, cuda), kd, dx=dx0)
+    check_vs_f32("dx", dx[:, :H].cpu().numpy(), ref[2], tor[2])
     assert (dx[:, H:] == -5.0).all()
 
 
@@ -262,9 +240,9 @@ def test_hgnn_kernels_vs_restatement(cuda, n, H, d, layers):
     tor = R.hgnn_grad(Pi[:, :H], Pu[:, :H], X, layers, g, dtype=torch.float32)
 
     def run():
-        a, b, c = _dev(Pi, cuda, True), _dev(Pu, cuda, True), _dev(X, cuda, True)
+        a, b, c = dev(Pi, cuda, True), dev(Pu, cuda, True), dev(X, cuda, True)
         out = LG._Hgnn.apply(a, b, c, H, layers)
-        out.backward(_dev(g, cuda))
+        out.backward(dev(g, cuda))
         return [t.cpu().numpy() for t in (out.detach(), a.grad, b.grad, c.grad)]
 
     got = run()
@@ -278,9 +256,9 @@ def test_hgnn_kernels_vs_restatement(cuda, n, H, d, layers):
     ratio = float((np.abs(got[0] - ref[0]) / (1e-5 * mag + 1e-30)).max())
     print(f"n={n} H={H} d={d} layers={layers}: forward err / bound {ratio:.3f}")
     assert np.all(np.isfinite(got[0])) and ratio <= 1.0
-    _check("gPi", got[1][:, :H], ref[1], tor[1])
-    _check("gPu", got[2][:, :H], ref[2], tor[2])
-    _check("gX", got[3], ref[3], tor[3])
+    check_vs_f32("gPi", got[1][:, :H], ref[1], tor[1])
+    check_vs_f32("gPu", got[2][:, :H], ref[2], tor[2])
+    check_vs_f32("gX", got[3], ref[3], tor[3])
     assert not got[1][:, H:].any() and not got[2][:, H:].any()
     for a, b in zip(got, run()):  # deterministic
         assert _bits(a, b)
@@ -295,7 +273,7 @@ def test_hgnn_primitives(cuda):
     n, n2, H, d, ld = 301, 77, 12, 64, 32
     f = lambda *s: rng.standard_normal(s).astype(np.float32)  # noqa: E731
     P, P2, X, X2, lat = f(n, ld), f(n2, ld), f(n, d), f(n2, d), f(H, d)
-    Pd, P2d, Xd, X2d, latd = (_dev(t, cuda) for t in (P, P2, X, X2, lat))
+    Pd, P2d, Xd, X2d, latd = (dev(t, cuda) for t in (P, P2, X, X2, lat))
     f64 = lambda a: a.astype(np.float64)  # noqa: E731
     want = f64(P[:, :H]).T @ f64(X) + f64(P2[:, :H]).T @ f64(X2)
     mag = np.abs(f64(P[:, :H])).T @ np.abs(f64(X)) + np.abs(f64(P2[:, :H])).T @ np.abs(f64(X2))
@@ -304,14 +282,14 @@ def test_hgnn_primitives(cuda):
     got = LG.hgnn_expand(Pd, H, latd).cpu().numpy()
     assert (np.abs(got - f64(P[:, :H]) @ f64(lat)) <= 1e-5 * (np.abs(f64(P[:, :H])) @ np.abs(f64(lat)))).all()
     base = f(n, ld)
-    got = LG.hgnn_rowdots(Xd, latd, ld, out=_dev(base, cuda), accumulate=True).cpu().numpy()
+    got = LG.hgnn_rowdots(Xd, latd, ld, out=dev(base, cuda), accumulate=True).cpu().numpy()
     want = f64(base[:, :H]) + f64(X) @ f64(lat).T
     mag = np.abs(f64(base[:, :H])) + np.abs(f64(X)) @ np.abs(f64(lat)).T
     assert (np.abs(got[:, :H] - want) <= 1e-5 * mag).all() and np.array_equal(got[:, H:], base[:, H:])
     with pytest.raises(RuntimeError, match="RSX_ERR_UNSUPPORTED"):
-        LG.hgnn_reduce(_dev(f(8, 96), cuda), _dev(f(8, 64), cuda), 68)
+        LG.hgnn_reduce(dev(f(8, 96), cuda), dev(f(8, 64), cuda), 68)
     with pytest.raises(RuntimeError, match="RSX_ERR_UNSUPPORTED"):
-        LG.hgnn_expand(Pd, H, _dev(f(H, 32), cuda))
+        LG.hgnn_expand(Pd, H, dev(f(H, 32), cuda))
 
 
 # ------------------------------------------------------------------ 4. the loss
@@ -329,9 +307,9 @@ def _run_loss(tabs, trip, nu, alpha, reg, cuda):
     from rsx import lgmrec as LG
 
     ws = LG.loss_workspace(trip.shape[1], tabs[0].shape[1], cuda)
-    ts = [_dev(t, cuda, True) for t in tabs]
+    ts = [dev(t, cuda, True) for t in tabs]
     keep = {}
-    loss = LG._LgmLoss.apply((nu, alpha, reg, ws, keep), _dev(trip, cuda), *ts)
+    loss = LG._LgmLoss.apply((nu, alpha, reg, ws, keep), dev(trip, cuda), *ts)
     loss.backward()
     out = keep["terms"].detach().cpu().numpy()
     assert out[0] == loss.item() or (np.isnan(out[0]) and np.isnan(loss.item()))
@@ -358,7 +336,7 @@ def test_loss_kernel_vs_restatement(cuda, d, B, nu, ni):
         rows = np.concatenate([trip[0], nu + trip[1], nu + trip[2]])
         off = np.setdiff1d(np.arange(nu + ni), rows)
         for name, g, r, t in zip(NAMES5, got[1], ref[1], tor[1]):
-            _check(name, g, r, t)
+            check_vs_f32(name, g, r, t)
             assert not g[off].any()
         again = _run_loss(tabs, trip, nu, alpha, reg, cuda)  # deterministic
         assert _bits(got[0], again[0]) and all(_bits(a, b) for a, b in zip(got[1], again[1]))
@@ -415,49 +393,26 @@ HP = R.HPARAMS
 
 
 def _setup(tmp_path, extra=None, feats="both"):
-    from rsx.config import Config
-    from rsx.data import EvalDataLoader, RecDataset, TrainDataLoader
-
     z0, z = R.load("lgmrec_step0_small.npz"), R.load("lgmrec_small.npz")
-    d = tmp_path / "data" / "baby"
-    d.mkdir(parents=True)
-    shutil.copy(os.path.join(R.GOLD, "gold_small.inter"), d / "baby.inter")
-    if feats in ("both", "image", "narrow"):
-        np.save(d / "image_feat_raw.npy", z["v_feat"])
-    if feats in ("both", "text"):
-        np.save(d / "text_feat_raw.npy", z["t_feat"])
-    if feats == "narrow":  # a text table whose width is no multiple of 4
-        np.save(d / "text_feat_raw.npy", z["t_feat"][:, :6])
-    cfg = dict(data_path=str(tmp_path / "data") + "/", train_batch_size=512, eval_batch_size=256, rsx_sampler="host",
-               is_multimodal_model=True)
+    # narrow: a text table whose width is no multiple of 4
+    text = {"both": z["t_feat"], "text": z["t_feat"], "narrow": z["t_feat"][:, :6]}.get(feats)
+    write_dataset(tmp_path, z["v_feat"] if feats != "text" else None, text)
+    cfg = dict(is_multimodal_model=True)
     cfg.update({k: v for k, v in HP.items() if k not in ("train_batch_size",)})
     cfg.update(extra or {})
-    c = Config("LGMRec", "baby", cfg)
-    for k in c["hyper_parameters"]:
-        if isinstance(c[k], list):
-            c[k] = c[k][0]
-    ds = RecDataset(c)
-    tr, va, te = ds.split()
-    for s in (ds, tr, va, te):
-        str(s)
-    train = TrainDataLoader(c, tr, batch_size=512, shuffle=True)
-    valid = EvalDataLoader(c, va, additional_dataset=tr, batch_size=256)
+    c, train, valid, _ = loaders("LGMRec", tmp_path, cfg)
     return z0, z, c, train, valid
 
 
 def _model(c, train):
-    from rsx.utils import get_model, init_seed
-
-    init_seed(c["seed"])
-    train.pretrain_setup()
-    return get_model("LGMRec")(c, train)
+    return make_model("LGMRec", c, train)
 
 
 def _draws(z, prefix, cuda):
     """The recorded draws as the model takes them: four noise tensors, then the packed keep masks."""
-    out = [_dev(z[f"{prefix}noise{k}"], cuda) for k in range(4)]
+    out = [dev(z[f"{prefix}noise{k}"], cuda) for k in range(4)]
     if f"{prefix}keep0" in z:
-        out += [_dev(z[f"{prefix}keep{k}"].view(np.int32), cuda) for k in range(4)]
+        out += [dev(z[f"{prefix}keep{k}"].view(np.int32), cuda) for k in range(4)]
     return out
 
 
@@ -466,8 +421,6 @@ def _param(z0, z, key, n):
 
 
 def test_lgmrec_init_graphs_forward(cuda, tmp_path):
-    from helpers import coo_sorted, csr_to_sorted
-
     z0, z, c, train, _ = _setup(tmp_path)
     m = _model(c, train)
     named = dict(m.named_parameters())
@@ -508,7 +461,7 @@ def test_lgmrec_first_two_steps(cuda, tmp_path):
     for s in (0, 1):
         pre = f"step{s}_"
         opt.zero_grad(set_to_none=True)
-        loss = m.calculate_loss(_dev(z0[pre + "triplets"].astype(np.int64), cuda), draws=_draws(z0, pre, cuda))
+        loss = m.calculate_loss(dev(z0[pre + "triplets"].astype(np.int64), cuda), draws=_draws(z0, pre, cuda))
         loss.backward()
         want = z0[pre + "terms"]  # bpr, ssl_u, ssl_i, the norms' sum over B
         got = [m.last_terms[1].item(), m.last_ssl[0].item(), m.last_ssl[1].item(), m.last_terms[2].item()]
@@ -536,7 +489,6 @@ def test_lgmrec_epoch_and_scores_vs_reference(cuda, tmp_path):
     """One epoch through the Trainer with every draw replayed (eager steps: a captured step
     would replay the first batch's draw tensors), then the reference's first two evaluation
     batches under their draws."""
-    from helpers import topk_equal_modulo_ties
     from rsx.trainer import Trainer
 
     z0, z, c, train, valid = _setup(tmp_path, dict(rsx_graph_step=False))
@@ -552,7 +504,7 @@ def test_lgmrec_epoch_and_scores_vs_reference(cuda, tmp_path):
     total = 0.0
     for k in range(nb):
         step["k"] = k
-        total += float(t.train_step(_dev(trip[:, 512 * k: 512 * (k + 1)], cuda), k)[1])
+        total += float(t.train_step(dev(trip[:, 512 * k: 512 * (k + 1)], cuda), k)[1])
     del m.calculate_loss
     torch.cuda.synchronize()
     print(f"epoch loss {total:.6f} vs reference {float(z['epoch0_loss']):.6f}")
@@ -566,7 +518,7 @@ def test_lgmrec_epoch_and_scores_vs_reference(cuda, tmp_path):
         assert err <= 5e-5 * scale, n
     m.eval()
     for b in range(2):
-        users = _dev(z[f"eval_b{b}_users"].astype(np.int64), cuda)
+        users = dev(z[f"eval_b{b}_users"].astype(np.int64), cuda)
         want = z[f"eval_b{b}_scores"]
         m._eval_cache = m._eval_tables(_draws(z, f"eval_b{b}_", cuda))
         scores = m.full_sort_predict([users, None]).cpu().numpy()
@@ -612,7 +564,7 @@ def test_lgmrec_mf_backbone_and_wide_hypergraph(cuda, tmp_path):
     rng = np.random.default_rng(5)
     noise = [_gumbel(rng, (n, 12)) for n in (ni, nu, ni, nu)]
     trip = z0["step0_triplets"].astype(np.int64)
-    loss = m.calculate_loss(_dev(trip, cuda), draws=[_dev(g, cuda) for g in noise])
+    loss = m.calculate_loss(dev(trip, cuda), draws=[dev(g, cuda) for g in noise])
     loss.backward()
 
     def ref(dtype):
@@ -627,7 +579,7 @@ def test_lgmrec_mf_backbone_and_wide_hypergraph(cuda, tmp_path):
     _check_word("loss", loss.item(), r64[0], r32[0])
     for n, p in m.named_parameters():
         if n in R.NAMES:
-            _check(n, p.grad.cpu().numpy(), r64[1][n], r32[1][n])
+            check_vs_f32(n, p.grad.cpu().numpy(), r64[1][n], r32[1][n])
 
 
 # ------------------------------------------------------------------ 6. capture
@@ -646,7 +598,7 @@ def _steps(tmp_path, tag, z, cuda, graph, draws):
     trip = z["step0_triplets"].astype(np.int64)
     losses = []
     for k in range(4):
-        losses.append(t.train_step(_dev(np.roll(trip, 37 * k, axis=1), cuda), k)[1])
+        losses.append(t.train_step(dev(np.roll(trip, 37 * k, axis=1), cuda), k)[1])
     torch.cuda.synchronize()
     return m, [float(x) for x in losses], t._graph.replays if t._graph is not None else 0
 
@@ -656,9 +608,7 @@ def test_lgmrec_captured_step_equals_eager(cuda, tmp_path):
     a, la, ra = _steps(tmp_path, "graph", z0, cuda, True, True)
     b, lb, rb = _steps(tmp_path, "eager", z0, cuda, False, True)
     assert ra == 3 and rb == 0  # batch 0 eager, batch 1 captured and replayed, batches 2 and 3 replays
-    assert la == lb
-    for (n, p), q in zip(a.named_parameters(), b.parameters()):
-        assert torch.equal(p, q), n
+    assert_same_run(a, b, la, lb)
 
 
 def test_lgmrec_hashed_draws_follow_the_seed(cuda, tmp_path):
@@ -669,16 +619,15 @@ def test_lgmrec_hashed_draws_follow_the_seed(cuda, tmp_path):
     z0 = R.load("lgmrec_step0_small.npz")
     a, la, ra = _steps(tmp_path, "a", z0, cuda, True, False)
     b, lb, _ = _steps(tmp_path, "b", z0, cuda, True, False)
-    assert ra == 3 and la == lb
-    for (n, p), q in zip(a.named_parameters(), b.parameters()):
-        assert torch.equal(p, q), n
+    assert ra == 3
+    assert_same_run(a, b, la, lb)
     # the same batch twice through the captured step, the optimiser's step size zero
     _, _, c, train, _ = _setup(tmp_path / "c", dict(rsx_graph_step=True, learning_rate=0.0))
     m = _model(c, train)
     t = Trainer(c, m)
     m.train()
     t._gate = False
-    batch = _dev(z0["step0_triplets"].astype(np.int64), cuda)
+    batch = dev(z0["step0_triplets"].astype(np.int64), cuda)
     seed0 = int(m._seed.item())
     losses = [float(t.train_step(batch, k)[1]) for k in range(4)]
     assert t._graph.replays == 3 and int(m._seed.item()) == seed0 + 4
@@ -692,7 +641,7 @@ def test_lgmrec_noise_only_draws_advance_the_seed(cuda, tmp_path):
     z0, z, c, train, _ = _setup(tmp_path)
     m = _model(c, train)
     m.train()
-    batch = _dev(z0["step0_triplets"].astype(np.int64), cuda)
+    batch = dev(z0["step0_triplets"].astype(np.int64), cuda)
     noise = _draws(z0, "step0_", cuda)[:4]
     seed0 = int(m._seed.item())
     with torch.no_grad():

@@ -5,29 +5,21 @@ the dense Adam, fused = autograd, the Trainer end to end against the reference's
 
 Observed figures are printed before every assertion (run with -s to see them)."""
 import ctypes as C
-import os
-import shutil
-
 import numpy as np
 import pytest
 import torch
 
 import mf_ref as R
-from helpers import metric_dict
+from helpers import dev, loaders, make_model, metric_dict, quick_start_case, record_batches, write_dataset
 
 pytestmark = pytest.mark.gpu
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 MODELS = ("BPR", "VBPR")
 REG = 2.0
 U24 = 2.0 ** -24
 NS = (1, 33, 1029)
 INS = (4, 72, 100, 1028)
 N_SRC = 57  # fewer table rows than the largest n: repeated, unsorted row indices
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 # ------------------------------------------------------------------ 1, 2: the Linear kernels
@@ -63,13 +55,13 @@ def test_linear_rows_fwd(cuda, lin_cases, o):
     for i in INS:
         for n in NS:
             c = lin_cases[(n, i, o)]
-            x, W, b = _dev(c["x"]), _dev(c["W"]), _dev(c["b"])
+            x, W, b = dev(c["x"], cuda), dev(c["W"], cuda), dev(c["b"], cuda)
             for rows in (c["rows"], None):
                 src = c["x"][rows] if rows is not None else c["x"][:n]
                 want, bound = _fwd_ref(src, c["W"], c["b"])
                 out = torch.full((n, 2 * o), 7.5, dtype=torch.float32, device=cuda)  # ld_out = 2 out_dim
                 xin = x if rows is not None else x[:n].contiguous()
-                ops.linear_rows_fwd(xin, W, b, None if rows is None else _dev(rows), out=out, col0=o)
+                ops.linear_rows_fwd(xin, W, b, None if rows is None else dev(rows, cuda), out=out, col0=o)
                 got = out.cpu().numpy()
                 assert np.all(got[:, :o] == 7.5), (n, i, o)  # the sentinel half survives
                 err = np.abs(got[:, o:] - want)
@@ -77,7 +69,7 @@ def test_linear_rows_fwd(cuda, lin_cases, o):
                 assert np.all(err <= bound), (n, i, o, rows is None, float((err / bound).max()))
             # no bias
             want, bound = _fwd_ref(c["x"][c["rows"]], c["W"], np.zeros(o, np.float32))
-            got = ops.linear_rows_fwd(x, W, None, _dev(c["rows"])).cpu().numpy()
+            got = ops.linear_rows_fwd(x, W, None, dev(c["rows"], cuda)).cpu().numpy()
             assert np.all(np.abs(got - want) <= bound)
     print(f"linear_rows_fwd out_dim {o}: worst error / bound = {worst:.3f}")
 
@@ -104,7 +96,7 @@ def test_linear_rows_fwd_wide_strips(cuda, row_tiles, o, ot):
     rows = rng.integers(0, N_SRC, n).astype(np.int64)
     want, bound = _fwd_ref(x[rows], W, b)
     out = torch.full((n, 2 * o), 7.5, dtype=torch.float32, device=cuda)
-    ops.linear_rows_fwd(_dev(x), _dev(W), _dev(b), _dev(rows), out=out, col0=o)
+    ops.linear_rows_fwd(dev(x, cuda), dev(W, cuda), dev(b, cuda), dev(rows, cuda), out=out, col0=o)
     got = out.cpu().numpy()
     assert np.all(got[:, :o] == 7.5)
     assert np.all(np.abs(got[:, o:] - want) <= bound), (n, o)
@@ -129,7 +121,7 @@ def test_linear_rows_wgrad(cuda, lin_cases, o):
     for i in INS:
         for n in NS:
             c = lin_cases[(n, i, o)]
-            x, g, rows = _dev(c["x"]), _dev(c["g"]), _dev(c["rows"])
+            x, g, rows = dev(c["x"], cuda), dev(c["g"], cuda), dev(c["rows"], cuda)
             g64, x64 = c["g"][:, :o].astype(np.float64), c["x"][c["rows"]].astype(np.float64)
             want = g64.T @ x64
             bound = 2 * n * U24 * (np.abs(g64).T @ np.abs(x64))
@@ -152,41 +144,22 @@ def test_linear_rows_wgrad(cuda, lin_cases, o):
 
 
 # ------------------------------------------------------------------ models on the fixture data
-def _setup(tmp_path, model, extra):
-    from rsx.config import Config
-    from rsx.data import EvalDataLoader, RecDataset, TrainDataLoader
+def _feats(model):
+    """(image, text) feature tables of the model's dataset directory: VBPR's, none for BPR."""
+    if model != "VBPR":
+        return None, None
+    z = R.load_fixture("VBPR")
+    return z["v_feat"], z["t_feat"]
 
-    d = tmp_path / "data" / "baby"
-    d.mkdir(parents=True, exist_ok=True)
-    shutil.copy(os.path.join(GOLD, "gold_small.inter"), d / "baby.inter")
-    if model == "VBPR":
-        z = R.load_fixture("VBPR")
-        np.save(d / "image_feat_raw.npy", z["v_feat"])
-        np.save(d / "text_feat_raw.npy", z["t_feat"])
-    cfg = dict(data_path=str(tmp_path / "data") + "/", train_batch_size=512, eval_batch_size=256,
-               rsx_sampler="host", is_multimodal_model=model == "VBPR")
-    cfg.update(extra)
-    c = Config(model, "baby", cfg)
-    for k in c["hyper_parameters"]:
-        if isinstance(c[k], list):
-            c[k] = c[k][0]
-    ds = RecDataset(c)
-    tr, va, te = ds.split()
-    for x in (ds, tr, va, te):
-        str(x)
-    train = TrainDataLoader(c, tr, batch_size=512, shuffle=True)
-    valid = EvalDataLoader(c, va, additional_dataset=tr, batch_size=256)
-    test = EvalDataLoader(c, te, additional_dataset=tr, batch_size=256)
-    return c, train, valid, test
+
+def _setup(tmp_path, model, extra):
+    write_dataset(tmp_path, *_feats(model))
+    return loaders(model, tmp_path, {"is_multimodal_model": model == "VBPR", **extra})
 
 
 def _model(tmp_path, name, extra=None):
-    from rsx.utils import get_model, init_seed
-
     c, train, valid, test = _setup(tmp_path, name, extra or {})
-    init_seed(c["seed"])
-    train.pretrain_setup()
-    return get_model(name)(c, train), c, train, valid, test
+    return make_model(name, c, train), c, train, valid, test
 
 
 def _named(m, name):
@@ -301,16 +274,7 @@ def _train(tmp_path, name, extra, epochs, record=False):
     m, c, train, valid, test = _model(tmp_path, name, extra)
     t = Trainer(c, m)
     assert t.fused
-    rec = []
-    if record:
-        orig = train._next_batch_data
-
-        def wrapped():
-            b = orig()
-            rec.append(b.cpu().clone())
-            return b
-
-        train._next_batch_data = wrapped
+    rec = record_batches(train) if record else []
     for epoch in range(epochs):
         m.cur_epoch = epoch
         m.pre_epoch_processing()
@@ -404,22 +368,7 @@ def test_captured_step_replays(cuda, name):
 # ------------------------------------------------------------------ 9: quick_start
 @pytest.mark.parametrize("name", MODELS)
 def test_quick_start(cuda, tmp_path, name):
-    from rsx.quick_start import quick_start
-
-    d = tmp_path / "data" / "baby"
-    d.mkdir(parents=True)
-    shutil.copy(os.path.join(GOLD, "gold_small.inter"), d / "baby.inter")
-    if name == "VBPR":
-        z = R.load_fixture("VBPR")
-        np.save(d / "image_feat_raw.npy", z["v_feat"])
-        np.save(d / "text_feat_raw.npy", z["t_feat"])
-    cwd = os.getcwd()
-    os.chdir(tmp_path)
-    try:
-        res = quick_start(name, "baby", {"data_path": str(tmp_path / "data") + "/", "epochs": 2,
-                                         "reg_weight": [1e-2], "train_batch_size": 512}, log=False)
-    finally:
-        os.chdir(cwd)
+    res = quick_start_case(name, tmp_path, *_feats(name), {"epochs": 2, "reg_weight": [1e-2]})
     assert len(res) == 1 and "recall@20" in res[0][1]
 
 

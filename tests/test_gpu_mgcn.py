@@ -11,37 +11,16 @@ measured against the reference's ops, never against the kernel.
 
 The rows form sums repeated rows per occurrence in a fixed order (no float atomics): two
 runs are bit-equal, and the captured graph step equals the eager one bit for bit."""
-import os
-import shutil
-
 import numpy as np
 import pytest
 import torch
 
 import mgcn_ref as R
-from helpers import coo_sorted, csr_to_sorted, metric_dict, topk_equal_modulo_ties
+from helpers import (assert_same_run, check_eval, check_params, check_vs_f32, coo_sorted, csr_to_sorted, dev, loaders,
+                     make_model, quick_start_case, record_batches, train_epochs, write_dataset)
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(64, 5), (64, 65), (128, 37), (64, 1001)]
-
-
-def _dev(a, cuda, grad=False):
-    t = torch.from_numpy(np.ascontiguousarray(a)).to(cuda)
-    return t.requires_grad_(True) if grad else t
-
-
-def _check(name, got, ref, tor):
-    """|got - ref| within max(1e-4 scale, 4 |torch f32 - ref|)."""
-    ref = np.asarray(ref)
-    got = np.asarray(got, dtype=np.float64).reshape(ref.shape)
-    tor = np.asarray(tor, dtype=np.float64).reshape(ref.shape)
-    scale = float(np.abs(ref).max())
-    terr = float(np.abs(tor - ref).max())
-    bound = max(1e-4 * scale, 4 * terr)
-    err = float(np.abs(got - ref).max())
-    print(f"  {name}: err {err:.3e}, scale {scale:.3e}, torch f32 err {terr:.3e}, bound {bound:.3e}")
-    assert np.all(np.isfinite(got)), name
-    assert err <= bound, name
 
 
 # ------------------------------------------------------------------ purifier
@@ -71,24 +50,24 @@ def test_purifier_vs_restatement(cuda, d, n):
     x = _purify_inputs(d, n, 10 + n)
     ref = R.purify(x["item"], x["feat"], x["W"], x["b"], gout=x["go"])
     tor = _torch_purify(x)
-    item = _dev(x["item"], cuda, True)
-    feat, W, b = ([_dev(a, cuda, True) for a in x[k]] for k in ("feat", "W", "b"))
+    item = dev(x["item"], cuda, True)
+    feat, W, b = ([dev(a, cuda, True) for a in x[k]] for k in ("feat", "W", "b"))
     out = MF._Purify.apply(feat[0], feat[1], item, W[0], b[0], W[1], b[1])
-    torch.autograd.backward(out, [_dev(g, cuda) for g in x["go"]])
+    torch.autograd.backward(out, [dev(g, cuda) for g in x["go"]])
     c = lambda t: t.detach().cpu().numpy()  # noqa: E731
     for m in range(2):
-        _check(f"out[{m}]", c(out[m]), ref["out"][m], tor["out"][m])
-        _check(f"g_feat[{m}]", c(feat[m].grad), ref["g_feat"][m], tor["g_feat"][m])
-        _check(f"dW[{m}]", c(W[m].grad), ref["dW"][m], tor["dW"][m])
-        _check(f"db[{m}]", c(b[m].grad), ref["db"][m], tor["db"][m])
-    _check("g_item", c(item.grad), ref["g_item"], tor["g_item"])
+        check_vs_f32(f"out[{m}]", c(out[m]), ref["out"][m], tor["out"][m])
+        check_vs_f32(f"g_feat[{m}]", c(feat[m].grad), ref["g_feat"][m], tor["g_feat"][m])
+        check_vs_f32(f"dW[{m}]", c(W[m].grad), ref["dW"][m], tor["dW"][m])
+        check_vs_f32(f"db[{m}]", c(b[m].grad), ref["db"][m], tor["db"][m])
+    check_vs_f32("g_item", c(item.grad), ref["g_item"], tor["g_item"])
     # one upstream gradient absent (NULL = zero)
     item.grad = None
     out = MF._Purify.apply(feat[0].detach(), feat[1].detach(), item, W[0].detach(), b[0].detach(), W[1].detach(),
                            b[1].detach())
-    out[1].backward(_dev(x["go"][1], cuda))
+    out[1].backward(dev(x["go"][1], cuda))
     half = R.purify(x["item"], x["feat"], x["W"], x["b"], gout=[None, x["go"][1]])
-    _check("g_item (image gradient absent)", c(item.grad), half["g_item"], half["g_item"])
+    check_vs_f32("g_item (image gradient absent)", c(item.grad), half["g_item"], half["g_item"])
 
 
 # --------------------------------------------------------------------- fuser
@@ -149,11 +128,11 @@ def _torch_fuse(x):
 def _run_fuse(x, cuda):
     from rsx import mgcn_fuse as MF
 
-    C, I, T = (_dev(x[k], cuda, True) for k in ("C", "I", "T"))  # noqa: E741
-    w = [_dev(x[k], cuda, True) for k in WKEYS]
-    rows = None if x["rows"] is None else _dev(np.asarray(x["rows"], dtype=np.int64), cuda)
+    C, I, T = (dev(x[k], cuda, True) for k in ("C", "I", "T"))  # noqa: E741
+    w = [dev(x[k], cuda, True) for k in WKEYS]
+    rows = None if x["rows"] is None else dev(np.asarray(x["rows"], dtype=np.int64), cuda)
     out = MF._Fuse.apply(C, I, T, rows, *w)
-    gs = [_dev(x["gA"], cuda), _dev(x["gS"], cuda)] + ([] if rows is None else [_dev(x["gCi"], cuda)])
+    gs = [dev(x["gA"], cuda), dev(x["gS"], cuda)] + ([] if rows is None else [dev(x["gCi"], cuda)])
     torch.autograd.backward(out, gs)
     c = lambda t: t.detach().cpu().numpy()  # noqa: E731
     r = dict(all=c(out[0]), side=c(out[1]), gC=c(C.grad), gI=c(I.grad), gT=c(T.grad))
@@ -165,7 +144,7 @@ def _run_fuse(x, cuda):
 
 def _check_fuse(got, ref, tor, keys):
     for k in keys:
-        _check(k, got[k], ref[k], tor[k])
+        check_vs_f32(k, got[k], ref[k], tor[k])
 
 
 @pytest.mark.parametrize("variant", ["plain", "saturate", "equal"])
@@ -222,41 +201,15 @@ def test_fuser_rows_form(cuda, d, case):
 
 # --------------------------------------------------------------------- model
 def _setup(tmp_path, extra=None, feats=None):
-    from rsx.config import Config
-    from rsx.data import EvalDataLoader, RecDataset, TrainDataLoader
-
     z = R.load_fixture()
-    d = tmp_path / "data" / "baby"
-    d.mkdir(parents=True)
-    shutil.copy(os.path.join(R.GOLD, "gold_small.inter"), d / "baby.inter")
-    v, t = feats if feats is not None else (z["v_feat"], z["t_feat"])
-    if v is not None:
-        np.save(d / "image_feat_raw.npy", v)
-    if t is not None:
-        np.save(d / "text_feat_raw.npy", t)
-    cfg = dict(data_path=str(tmp_path / "data") + "/", train_batch_size=512, eval_batch_size=256, rsx_sampler="host",
-               is_multimodal_model=True, cl_loss=[0.01])
+    write_dataset(tmp_path, *(feats if feats is not None else (z["v_feat"], z["t_feat"])))
+    cfg = dict(is_multimodal_model=True, cl_loss=[0.01])
     cfg.update(extra or {})
-    c = Config("MGCN", "baby", cfg)
-    for k in c["hyper_parameters"]:
-        if isinstance(c[k], list):
-            c[k] = c[k][0]
-    ds = RecDataset(c)
-    tr, va, te = ds.split()
-    for s in (ds, tr, va, te):
-        str(s)
-    train = TrainDataLoader(c, tr, batch_size=512, shuffle=True)
-    valid = EvalDataLoader(c, va, additional_dataset=tr, batch_size=256)
-    test = EvalDataLoader(c, te, additional_dataset=tr, batch_size=256)
-    return z, c, train, valid, test
+    return (z,) + loaders("MGCN", tmp_path, cfg)
 
 
 def _model(c, train):
-    from rsx.utils import get_model, init_seed
-
-    init_seed(c["seed"])
-    train.pretrain_setup()
-    return get_model("MGCN")(c, train)
+    return make_model("MGCN", c, train)
 
 
 def test_mgcn_init_graphs_forward(cuda, tmp_path):
@@ -293,7 +246,7 @@ def test_mgcn_first_step(cuda, tmp_path):
     m = _model(c, train)
     m.train()
     opt = torch.optim.Adam(m.parameters(), lr=c["learning_rate"])
-    trip = _dev(z["step0_triplets"].astype(np.int64), cuda)
+    trip = dev(z["step0_triplets"].astype(np.int64), cuda)
     loss = m.calculate_loss(trip)
     loss.backward()
     want = float(z["step0_loss"])
@@ -329,7 +282,7 @@ def test_mgcn_batch_rows_loss_equals_full_tables(cuda, tmp_path):
     z, c, train, *_ = _setup(tmp_path)
     m = _model(c, train)
     m.train()
-    trip = _dev(z["step0_triplets"].astype(np.int64), cuda)
+    trip = dev(z["step0_triplets"].astype(np.int64), cuda)
     trip[0, :40] = trip[0, 0]
     trip[1, 100:140] = trip[2, 7]
     out = []
@@ -364,14 +317,12 @@ def _steps(tmp_path, tag, batches, graph):
 def test_mgcn_captured_step_equals_eager(cuda, tmp_path):
     z = R.load_fixture()
     trip = z["epoch0_triplets"].astype(np.int64)
-    seq = [_dev(trip[:, 512 * k: 512 * (k + 1)], cuda) for k in range(3)]
+    seq = [dev(trip[:, 512 * k: 512 * (k + 1)], cuda) for k in range(3)]
     a, la, ta = _steps(tmp_path, "graph", seq, True)
     b, lb, tb = _steps(tmp_path, "eager", seq, False)
     # batch 0 eager, batch 1 captured, batch 2 a replay
     assert ta._graph is not None and ta._graph.replays >= 1 and tb._graph is None
-    assert la == lb
-    for (n, p), q in zip(a.named_parameters(), b.parameters()):
-        assert torch.equal(p, q), n
+    assert_same_run(a, b, la, lb)
 
 
 def test_mgcn_trainer_vs_reference(cuda, tmp_path):
@@ -381,45 +332,14 @@ def test_mgcn_trainer_vs_reference(cuda, tmp_path):
     m = _model(c, train)
     t = Trainer(c, m)
     assert not t.fused and type(t.optimizer).__name__ == "RsxAdam"
-    rec, orig = [], train._next_batch_data
-
-    def wrapped():
-        b = orig()
-        rec.append(b.cpu().clone())
-        return b
-
-    train._next_batch_data = wrapped
-    losses = []
-    for epoch in range(2):
-        m.cur_epoch = epoch
-        m.pre_epoch_processing()
-        loss, _ = t._train_epoch(train, epoch)
-        assert not torch.is_tensor(loss) and np.isfinite(loss)
-        losses.append(loss)
-        t.lr_scheduler.step()
-        t._epoch_for_lr += 1
-    torch.cuda.synchronize()
+    rec = record_batches(train)
+    losses = train_epochs(t, m, train, 2)
     want = np.concatenate([z[f"epoch{e}_triplets"] for e in range(2)], axis=1).astype(np.int64)
     assert np.array_equal(torch.cat(rec, dim=1).numpy(), want)  # the recorded triplets
     assert t._graph is not None and t._graph.replays > 0
     print(f"epoch losses {losses} vs reference {z['epoch_losses']}")
-    for n, p in m.named_parameters():
-        w = z["epoch1_param." + n]
-        scale = float(np.abs(w).max())
-        err = float(np.abs(p.detach().cpu().numpy() - w).max())
-        print(f"  {n}: err / scale {err / scale:.2e} (bound 5e-5)")
-        assert err <= 5e-5 * scale, n
-    for split, loader in (("valid", valid), ("test", test)):
-        tag = f"epoch1_{split}"
-        res = t.evaluate(loader)
-        ref = metric_dict(z, tag)
-        assert res.keys() == ref.keys()
-        for k in ref:
-            assert abs(res[k] - ref[k]) <= 1e-4, (k, res[k], ref[k])
-        assert np.array_equal(loader.eval_u.cpu().numpy(), z[tag + "_users"])
-        _, idx = m.full_sort_topk([loader.eval_u, None], 50, loader)
-        scores = m.full_sort_predict([loader.eval_u, None]).cpu().numpy()
-        assert topk_equal_modulo_ties(idx.cpu().numpy(), z[tag + "_topk_idx"].astype(np.int64), scores) == 0
+    check_params(m, z, "epoch1_param.", 5e-5)
+    check_eval(t, m, z, (("valid", valid), ("test", test)))
     # training again invalidates the cached evaluation tables
     assert m._eval_cache is not None
     m.train()
@@ -446,20 +366,7 @@ def test_mgcn_unsupported_configurations_raise(cuda, tmp_path, what):
 def test_mgcn_quick_start(cuda, tmp_path):
     """`main.py -m MGCN -d <dataset>`'s path: trains an epoch and evaluates on a dataset
     directory with the .inter file and the two feature files."""
-    from rsx.quick_start import quick_start
-
     z = R.load_fixture()
-    d = tmp_path / "data" / "baby"
-    d.mkdir(parents=True)
-    shutil.copy(os.path.join(R.GOLD, "gold_small.inter"), d / "baby.inter")
-    np.save(d / "image_feat_raw.npy", z["v_feat"])
-    np.save(d / "text_feat_raw.npy", z["t_feat"])
-    cwd = os.getcwd()
-    os.chdir(tmp_path)
-    try:
-        res = quick_start("MGCN", "baby", {"data_path": str(tmp_path / "data") + "/", "epochs": 1, "cl_loss": [0.01],
-                                           "train_batch_size": 512}, log=False)
-    finally:
-        os.chdir(cwd)
+    res = quick_start_case("MGCN", tmp_path, z["v_feat"], z["t_feat"], {"epochs": 1, "cl_loss": [0.01]})
     assert len(res) == 1 and "recall@20" in res[0][1]
     assert all(np.isfinite(v) for v in res[0][1].values())

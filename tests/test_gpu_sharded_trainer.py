@@ -16,7 +16,7 @@ import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
-from helpers import init_pg, store_path
+from helpers import init_pg, store_path, take_first
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -30,9 +30,7 @@ def _setup(root, **extra):
                n_layers=[3], reg_weight=[1e-2], rsx_dist_backend="gloo")
     cfg.update(extra)
     c = Config("LightGCN", "baby", cfg)
-    for k in c["hyper_parameters"]:
-        if isinstance(c[k], list):
-            c[k] = c[k][0]
+    take_first(c)
     ds = RecDataset(c)
     tr, va, te = ds.split()
     for x in (ds, tr, va, te):

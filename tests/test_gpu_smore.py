@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import coo_sorted, csr_to_sorted, metric_dict
+from helpers import coo_sorted, csr_to_sorted, metric_dict, take_first
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -40,9 +40,7 @@ def _setup(tmp_path, golden, fx="smore_small"):
                                       eval_batch_size=256, rsx_sampler="host", is_multimodal_model=True,
                                       dropout_rate=[0.0], mg_verbose=False, image_knn_k=[10], text_knn_k=[8],
                                       **extra))
-    for k in c["hyper_parameters"]:
-        if isinstance(c[k], list):
-            c[k] = c[k][0]
+    take_first(c)
     ds = RecDataset(c)
     tr, va, te = ds.split()
     for x in (ds, tr, va, te):

@@ -21,20 +21,12 @@ Usage:  python tools/bm3_step_time.py [--steps 200] [--repeats 5] [--warmup 30] 
 """
 from __future__ import annotations
 
-import argparse
 import json
-import os
-import sys
-import tempfile
-import types
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, "recommendar-systems_amd"))
+import torch
+import torch.nn.functional as F
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+from _step_time import alternated, captured, not_measured, parser, require_gpu, stage_times, synth_model, trainer_step
 
 
 def loss_bytes(nu: int, ni: int, d: int, B: int, S: int = 4) -> dict:
@@ -67,79 +59,15 @@ def torch_loss(m, E, H, T, V, P, pb, users, items):
         m.cl_weight * (cos(t_p, i_t) + cos(v_p, i_t) + cos(t_p, t_t) + cos(v_p, v_t))
 
 
-def build(args, root):
-    from rsx import synth
-    from rsx.bm3 import BM3
-    from rsx.config import Config
-    from rsx.utils import init_seed
-
-    df = synth.shaped("sports", seed=0, scale=args.scale)
-    df = df[df.x_label == 0]
-    nu, ni = int(df.userID.max()) + 1, int(df.itemID.max()) + 1
-    os.makedirs(os.path.join(root, "sports"))
-    np.save(os.path.join(root, "sports", "image_feat.npy"), synth.features(ni, 4096, seed=5))
-    np.save(os.path.join(root, "sports", "text_feat.npy"), synth.features(ni, 384, seed=6))
-    c = Config("BM3", "sports", dict(data_path=root + "/", train_batch_size=2048, n_layers=2, dropout=0.3,
-                                     reg_weight=0.1, seed=999))
-    from scipy.sparse import coo_matrix
-
-    ds = types.SimpleNamespace(get_user_num=lambda: nu, get_item_num=lambda: ni)
-    loader = types.SimpleNamespace(dataset=ds, inter_matrix=lambda form="coo": coo_matrix(
-        (np.ones(len(df)), (df.userID.values, df.itemID.values)), shape=(nu, ni)))
-    init_seed(999)
-    m = BM3(c, loader)
-    rng = np.random.default_rng(1)
-    sel = rng.permutation(len(df))[: 4 * 2048].reshape(4, 2048)
-    batches = [torch.from_numpy(np.stack([df.userID.values[s], df.itemID.values[s]]).astype(np.int64)).cuda()
-               for s in sel]
-    return m, c, batches
-
-
-class Timer:
-    def __init__(self, args):
-        self.a = args
-
-    def windows(self, run):
-        """ms per iteration of `repeats` windows of `steps` iterations: [median, min, max]."""
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for _ in range(self.a.warmup):
-            run()
-        torch.cuda.synchronize()
-        out = []
-        for _ in range(self.a.repeats):
-            e0.record()
-            for _ in range(self.a.steps):
-                run()
-            e1.record()
-            torch.cuda.synchronize()
-            out.append(e0.elapsed_time(e1) / self.a.steps)
-        out.sort()
-        return [round(out[len(out) // 2], 4), round(out[0], 4), round(out[-1], 4)]
-
-    def graphed(self, run):
-        run()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            run()
-        return self.windows(g.replay)
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=200, help="iterations per timed window")
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows (median, min, max reported)")
-    ap.add_argument("--warmup", type=int, default=30)
-    ap.add_argument("--scale", type=float, default=1.0, help="shrink the graph (a rehearsal)")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bm3_step_time: needs a GPU (step times are device measurements)")
+    args = parser(steps=200, warmup=30).parse_args()
+    require_gpu("bm3_step_time")
     from rsx import bm3
     from rsx.trainer import Trainer
 
-    tm = Timer(args)
-    with tempfile.TemporaryDirectory() as root:
-        m, c, batches = build(args, root)
+    # the batches are [user, item] pairs: BM3 draws no negatives
+    m, c, batches, _ = synth_model("BM3", "sports", args, dict(n_layers=2, dropout=0.3, reg_weight=0.1),
+                                   (("image_feat.npy", 4096, 5), ("text_feat.npy", 384, 6)), negatives=False)
     m.train()
     res = {"n_users": m.n_users, "n_items": m.n_items, "d": 64, "F": [4096, 384], "batch": 2048, "n_layers": 2,
            "dropout": 0.3, "steps_per_window": args.steps, "windows": args.repeats, "format": "[median, min, max] ms"}
@@ -153,21 +81,14 @@ def main():
     for name, calc in (("fused", fused_calc), ("torch_loss", torch_calc)):
         for graph in (False, True):
             m.calculate_loss = calc
-            c["rsx_graph_step"] = graph
-            t = Trainer(c, m)
-            k = [0]
-
-            def step():
-                t.train_step(batches[k[0] % len(batches)], k[0])
-                k[0] += 1
-
+            t, step = trainer_step(c, m, batches, graph)
             key = f"step_{name}_{'graph' if graph else 'eager'}"
             try:
-                res[key] = tm.windows(step)
+                res.update(alternated(args, {key: step}))
             except RuntimeError as e:  # a torch op that cannot be captured: reported, not hidden
                 if name == "fused":
                     raise
-                res[key] = "not measured: " + str(e).splitlines()[0][:120]
+                res[key] = not_measured(e, 120)
                 continue
             if graph:
                 assert t._graph is not None and t._graph.replays >= args.steps
@@ -191,13 +112,13 @@ def main():
     def torch_loss_part():
         torch.autograd.grad(torch_loss(m, *leaves, users, items), leaves)
 
-    res["loss_fused_eager"] = tm.windows(fused_loss)
-    res["loss_fused_graph"] = tm.graphed(fused_loss)
-    res["loss_torch_eager"] = tm.windows(torch_loss_part)
+    res.update(alternated(args, {"loss_fused_eager": fused_loss}))
+    res.update(alternated(args, {"loss_fused_graph": captured(fused_loss)}))
+    res.update(alternated(args, {"loss_torch_eager": torch_loss_part}))
     try:
-        res["loss_torch_graph"] = tm.graphed(torch_loss_part)
+        res.update(alternated(args, {"loss_torch_graph": captured(torch_loss_part)}))
     except RuntimeError as e:
-        res["loss_torch_graph"] = "not measured: " + str(e).splitlines()[0][:120]
+        res["loss_torch_graph"] = not_measured(e, 120)
     by = loss_bytes(m.n_users, m.n_items, 64, 2048)
     res["loss_algorithmic_bytes"] = by
     res["loss_fused_graph_bytes_per_s_over_8TBps"] = round(by["total"] / (res["loss_fused_graph"][0] * 1e-3) / 8e12, 4)
@@ -206,11 +127,9 @@ def main():
     opt = Trainer(c, m).optimizer
     names = ("prop_fwd", "proj_fwd", "loss_fwd_bwd", "proj_bwd", "prop_bwd", "adam")
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
-    acc = np.zeros(len(names))
     from rsx.blocks import _ego, _Project, _PropMean
 
-    n_split = args.warmup + args.steps
-    for it in range(n_split):
+    def one_step(it):
         opt.zero_grad(set_to_none=True)
         inter = batches[it % len(batches)]
         ev[0].record()
@@ -232,12 +151,9 @@ def main():
         ev[5].record()
         opt.step()
         ev[6].record()
-        torch.cuda.synchronize()
-        if it >= args.warmup:
-            acc += [ev[k].elapsed_time(ev[k + 1]) for k in range(len(names))]
-    split = {n: round(float(v) / args.steps, 4) for n, v in zip(names, acc)}
-    split["sum"] = round(float(acc.sum()) / args.steps, 4)
-    res["split_eager_ms"] = split
+        return loss
+
+    res["split_eager_ms"], _, loss = stage_times(args, names, ev, one_step)
     assert bool(torch.isfinite(loss))
     print(json.dumps(res), flush=True)
 

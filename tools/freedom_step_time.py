@@ -19,20 +19,13 @@ Usage:  python tools/freedom_step_time.py [--steps 100] [--repeats 5] [--warmup 
 """
 from __future__ import annotations
 
-import argparse
 import json
-import os
-import sys
-import tempfile
-import types
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, "recommendar-systems_amd"))
+import torch
+import torch.nn.functional as F
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+from _step_time import (alternated, captured, not_measured, parser, require_gpu, stage_times, synth_model,
+                        trainer_runs)
 
 
 # ------------------------------------------------------------ the comparator loss
@@ -79,72 +72,17 @@ def loss_bytes(n_users: int, n_items: int, d: int, B: int) -> dict:
             "bwd_zero_fill_bytes": (n_users + 3 * n_items) * row}
 
 
-def build(args, root):
-    from scipy.sparse import coo_matrix
-
-    from rsx import synth
-    from rsx.config import Config
-    from rsx.freedom import FREEDOM
-    from rsx.utils import init_seed
-
-    df = synth.shaped("sports", seed=0, scale=args.scale)
-    df = df[df.x_label == 0]
-    nu, ni = int(df.userID.max()) + 1, int(df.itemID.max()) + 1
-    os.makedirs(os.path.join(root, "sports"))
-    np.save(os.path.join(root, "sports", "image_feat.npy"), synth.features(ni, 4096, seed=5))
-    np.save(os.path.join(root, "sports", "text_feat.npy"), synth.features(ni, 384, seed=6))
-    c = Config("FREEDOM", "sports", dict(data_path=root + "/", train_batch_size=2048, dropout=0.8, reg_weight=0.001,
-                                         seed=999, is_multimodal_model=True))
-    ds = types.SimpleNamespace(get_user_num=lambda: nu, get_item_num=lambda: ni)
-    loader = types.SimpleNamespace(dataset=ds, inter_matrix=lambda form="coo": coo_matrix(
-        (np.ones(len(df)), (df.userID.values, df.itemID.values)), shape=(nu, ni)))
-    init_seed(999)
-    m = FREEDOM(c, loader)
-    rng = np.random.default_rng(1)
-    sel = rng.permutation(len(df))[: 4 * 2048].reshape(4, 2048)
-    batches = [torch.from_numpy(np.stack([df.userID.values[s], df.itemID.values[s],
-                                          rng.integers(0, ni, 2048)]).astype(np.int64)).cuda() for s in sel]
-    return m, c, batches, len(df)
-
-
-def alternated(args, runs: dict) -> dict:
-    """ms per iteration of each run in `runs`, their windows alternated: name -> [median, min, max]."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for run in runs.values():
-        for _ in range(args.warmup):
-            run()
-    torch.cuda.synchronize()
-    out = {k: [] for k in runs}
-    for _ in range(args.repeats):
-        for k, run in runs.items():
-            e0.record()
-            for _ in range(args.steps):
-                run()
-            e1.record()
-            torch.cuda.synchronize()
-            out[k].append(e0.elapsed_time(e1) / args.steps)
-    return {k: [round(sorted(v)[len(v) // 2], 4), round(min(v), 4), round(max(v), 4)] for k, v in out.items()}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=100, help="iterations per timed window")
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows per variant (median, min, max reported)")
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--scale", type=float, default=1.0, help="shrink the graph (a rehearsal)")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("freedom_step_time: needs a GPU (step times are device measurements)")
-    if args.repeats < 5:
-        raise SystemExit("freedom_step_time: at least 5 windows")
+    args = parser(steps=100, warmup=20).parse_args()
+    require_gpu("freedom_step_time", args)
     from rsx import freedom
     from rsx.blocks import _ego, _Project, ui_backbone
     from rsx.optim import RsxAdam
-    from rsx.trainer import Trainer
 
     fused = freedom._FreedomLoss
-    with tempfile.TemporaryDirectory() as root:
-        m, c, batches, n_edges = build(args, root)
+    m, c, batches, n_edges = synth_model(
+        "FREEDOM", "sports", args, dict(dropout=0.8, reg_weight=0.001, is_multimodal_model=True),
+        (("image_feat.npy", 4096, 5), ("text_feat.npy", 384, 6)))
     m.train()
     m.pre_epoch_processing()  # one epoch graph (device edge dropout) for every measurement
     d, B, nu, ni = m.embedding_dim, 2048, m.n_users, m.n_items
@@ -154,25 +92,14 @@ def main():
            "format": "[median, min, max] ms", "loss_bytes": loss_bytes(nu, ni, d, B)}
 
     # ---- whole steps through the Trainer, fused and torch loss alternated
-    for graph in (True, False):
-        c["rsx_graph_step"] = graph
-        runs = {}
-        for name, cls in (("fused", fused), ("torch_loss", TorchLoss)):
-            t = Trainer(c, m)
-            k = [0]
+    def use(cls):
+        def select():
+            freedom._FreedomLoss = cls
+        return select
 
-            def step(t=t, k=k, cls=cls):
-                freedom._FreedomLoss = cls
-                t.train_step(batches[k[0] % len(batches)], k[0])
-                k[0] += 1
-
-            runs[f"step_{name}_{'graph' if graph else 'eager'}"] = step
-        try:
-            res.update(alternated(args, runs))
-        except RuntimeError as e:
-            if not graph:
-                raise
-            res["step_graph"] = "not measured: " + str(e).splitlines()[0][:160]
+    # (this tool times the captured steps first, as it always has: its JSON lists them first)
+    res.update(trainer_runs(args, c, m, batches, {"fused": use(fused), "torch_loss": use(TorchLoss)},
+                            order=(True, False)))
     freedom._FreedomLoss = fused
 
     # ---- the loss alone, forward + backward on fixed tables
@@ -187,15 +114,10 @@ def main():
     res.update({k + "_eager": v for k, v in alternated(args, alone).items()})
     graphs = {}
     for name, run in alone.items():
-        run()
-        torch.cuda.synchronize()
-        cg = torch.cuda.CUDAGraph()
         try:
-            with torch.cuda.graph(cg):
-                run()
-            graphs[name + "_graph"] = cg.replay
+            graphs[name + "_graph"] = captured(run)
         except RuntimeError as e:
-            res[name + "_graph"] = "not measured: " + str(e).splitlines()[0][:160]
+            res[name + "_graph"] = not_measured(e)
     if graphs:
         res.update(alternated(args, graphs))
 
@@ -206,11 +128,10 @@ def main():
     names = ("ui_prop_fwd", "item_prop_fwd", "proj_fwd", "loss_fwd", "loss_bwd", "proj_bwd", "item_prop_bwd",
              "ui_prop_bwd", "adam_feature_tables", "adam_rest")
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
-    acc = np.zeros(len(names))
     leaf = lambda *xs: [None if x is None else x.detach().requires_grad_() for x in xs]  # noqa: E731
     off = torch.cat([torch.zeros(B, dtype=torch.int64), torch.full((2 * B,), nu)]).cuda()
 
-    def one_step(it, record):
+    def one_step(it):
         opt_feat.zero_grad(set_to_none=True)
         opt_rest.zero_grad(set_to_none=True)
         trip = batches[it % len(batches)]
@@ -238,16 +159,9 @@ def main():
         ev[9].record()
         opt_rest.step()
         ev[10].record()
-        torch.cuda.synchronize()
-        if record:
-            acc[:] += [ev[k].elapsed_time(ev[k + 1]) for k in range(len(names))]
         return loss
 
-    for it in range(args.warmup + args.steps):
-        loss = one_step(it, it >= args.warmup)
-    split = {n: round(float(v) / args.steps, 4) for n, v in zip(names, acc)}
-    total = float(acc.sum()) / args.steps
-    split["sum"] = round(total, 4)
+    split, acc, loss = stage_times(args, names, ev, one_step)
     split["share_projections"] = round(float(acc[2] + acc[5]) / float(acc.sum()), 4)
     split["share_adam_feature_tables"] = round(float(acc[8]) / float(acc.sum()), 4)
     split["share_loss"] = round(float(acc[3] + acc[4]) / float(acc.sum()), 4)
@@ -261,7 +175,8 @@ def main():
         n_prof = 10
         with profile(activities=[ProfilerActivity.CUDA]) as prof:
             for it in range(n_prof):
-                one_step(it, False)
+                one_step(it)
+                torch.cuda.synchronize()
         rows = [(e.key, e.count, getattr(e, "device_time_total", None) or getattr(e, "cuda_time_total", 0.0))
                 for e in prof.key_averages()]
         rows = [r for r in rows if r[2] > 0]

@@ -19,20 +19,12 @@ Usage:  python tools/lattice_step_time.py [--steps 100] [--repeats 5] [--warmup 
 """
 from __future__ import annotations
 
-import argparse
 import json
-import os
-import sys
-import tempfile
-import types
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, "recommendar-systems_amd"))
+import torch
+import torch.nn.functional as F
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+from _step_time import alternated, parser, require_gpu, synth_model, trainer_runs
 
 
 class TorchLoss:
@@ -71,71 +63,16 @@ class TorchProp:
         return h
 
 
-def build(args, root):
-    from scipy.sparse import coo_matrix
-
-    from rsx import synth
-    from rsx.config import Config
-    from rsx.lattice import LATTICE
-    from rsx.utils import init_seed
-
-    df = synth.shaped("sports", seed=0, scale=args.scale)
-    df = df[df.x_label == 0]
-    nu, ni = int(df.userID.max()) + 1, int(df.itemID.max()) + 1
-    os.makedirs(os.path.join(root, "sports"))
-    np.save(os.path.join(root, "sports", "image_feat.npy"), synth.features(ni, 4096, seed=5))
-    np.save(os.path.join(root, "sports", "text_feat.npy"), synth.features(ni, 384, seed=6))
-    c = Config("LATTICE", "sports", dict(data_path=root + "/", train_batch_size=2048, reg_weight=0.001,
-                                         learning_rate=0.001, seed=999, is_multimodal_model=True))
-    ds = types.SimpleNamespace(get_user_num=lambda: nu, get_item_num=lambda: ni)
-    loader = types.SimpleNamespace(dataset=ds, inter_matrix=lambda form="coo": coo_matrix(
-        (np.ones(len(df)), (df.userID.values, df.itemID.values)), shape=(nu, ni)))
-    init_seed(999)
-    m = LATTICE(c, loader)
-    rng = np.random.default_rng(1)
-    sel = rng.permutation(len(df))[: 4 * 2048].reshape(4, 2048)
-    batches = [torch.from_numpy(np.stack([df.userID.values[s], df.itemID.values[s],
-                                          rng.integers(0, ni, 2048)]).astype(np.int64)).cuda() for s in sel]
-    return m, c, batches, len(df)
-
-
-def alternated(args, runs: dict, steps=None) -> dict:
-    """ms per iteration of each run in `runs`, their windows alternated: name -> [median, min, max]."""
-    steps = steps or args.steps
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for run in runs.values():
-        for _ in range(min(args.warmup, steps)):
-            run()
-    torch.cuda.synchronize()
-    out = {k: [] for k in runs}
-    for _ in range(args.repeats):
-        for k, run in runs.items():
-            e0.record()
-            for _ in range(steps):
-                run()
-            e1.record()
-            torch.cuda.synchronize()
-            out[k].append(e0.elapsed_time(e1) / steps)
-    return {k: [round(sorted(v)[len(v) // 2], 4), round(min(v), 4), round(max(v), 4)] for k, v in out.items()}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=100, help="iterations per timed window")
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows per variant (median, min, max reported)")
-    ap.add_argument("--warmup", type=int, default=20)
+    ap = parser(steps=100, warmup=20)
     ap.add_argument("--builds", type=int, default=5, help="builds per timed window")
-    ap.add_argument("--scale", type=float, default=1.0, help="shrink the graph (a rehearsal)")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("lattice_step_time: needs a GPU (step times are device measurements)")
-    if args.repeats < 5:
-        raise SystemExit("lattice_step_time: at least 5 windows")
+    require_gpu("lattice_step_time", args)
     from rsx import lattice
-    from rsx.trainer import Trainer
 
-    with tempfile.TemporaryDirectory() as root:
-        m, c, batches, n_edges = build(args, root)
+    m, c, batches, n_edges = synth_model(
+        "LATTICE", "sports", args, dict(reg_weight=0.001, learning_rate=0.001, is_multimodal_model=True),
+        (("image_feat.npy", 4096, 5), ("text_feat.npy", 384, 6)))
     m.train()
     d, B, nu, ni = m.embedding_dim, 2048, m.n_users, m.n_items
     res = {"n_users": nu, "n_items": ni, "train_edges": n_edges, "d": d, "F": [4096, 384], "batch": B,
@@ -165,25 +102,12 @@ def main():
     m.pre_epoch_processing()
     m.calculate_loss(batches[0]).backward()  # the epoch's build: every later batch is steady
     m.zero_grad(set_to_none=True)
-    for graph in (False, True):  # the captures last: a failed capture leaves the stream unusable
-        c["rsx_graph_step"] = graph
-        runs = {}
-        for name, pair in (("hip", fused), ("torch_ops", (TorchLoss, TorchProp))):
-            t = Trainer(c, m)
-            k = [0]
+    def use(pair):
+        def select():
+            lattice._LatticeLoss, lattice._ItemProp = pair
+        return select
 
-            def step(t=t, k=k, pair=pair):
-                lattice._LatticeLoss, lattice._ItemProp = pair
-                t.train_step(batches[k[0] % len(batches)], k[0])
-                k[0] += 1
-
-            runs[f"step_{name}_{'graph' if graph else 'eager'}"] = step
-        try:
-            res.update(alternated(args, runs))
-        except RuntimeError as e:
-            if not graph:
-                raise
-            res["step_graph"] = "not measured: " + str(e).splitlines()[0][:160]
+    res.update(trainer_runs(args, c, m, batches, {"hip": use(fused), "torch_ops": use((TorchLoss, TorchProp))}))
     lattice._LatticeLoss, lattice._ItemProp = fused
 
     print(json.dumps(res))

@@ -20,20 +20,12 @@ Usage:  python tools/lgmrec_step_time.py [--steps 50] [--repeats 5] [--warmup 10
 """
 from __future__ import annotations
 
-import argparse
 import json
-import os
-import sys
-import tempfile
-import types
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, "recommendar-systems_amd"))
+import torch
+import torch.nn.functional as F
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+from _step_time import alternated, parser, require_gpu, synth_model, trainer_runs
 
 
 def torch_ssl(T1, T2, idx, tau):
@@ -44,72 +36,13 @@ def torch_ssl(T1, T2, idx, tau):
     return -torch.log(pos / ttl).sum()
 
 
-def build(args, root):
-    from scipy.sparse import coo_matrix
-
-    from rsx import synth
-    from rsx.config import Config
-    from rsx.lgmrec import LGMRec
-    from rsx.utils import init_seed
-
-    df = synth.shaped("baby", seed=0, scale=args.scale)
-    df = df[df.x_label == 0]
-    nu, ni = int(df.userID.max()) + 1, int(df.itemID.max()) + 1
-    os.makedirs(os.path.join(root, "baby"))
-    np.save(os.path.join(root, "baby", "image_feat_raw.npy"), synth.features(ni, 4096, seed=5))
-    np.save(os.path.join(root, "baby", "text_feat_raw.npy"), synth.features(ni, 384, seed=6))
-    c = Config("LGMRec", "baby", dict(data_path=root + "/", train_batch_size=2048, learning_rate=0.001, seed=999,
-                                      is_multimodal_model=True))
-    for k in c["hyper_parameters"]:
-        if isinstance(c[k], list):
-            c[k] = c[k][0]
-    ds = types.SimpleNamespace(get_user_num=lambda: nu, get_item_num=lambda: ni)
-    loader = types.SimpleNamespace(dataset=ds, inter_matrix=lambda form="coo": coo_matrix(
-        (np.ones(len(df)), (df.userID.values, df.itemID.values)), shape=(nu, ni)))
-    init_seed(999)
-    m = LGMRec(c, loader)
-    rng = np.random.default_rng(1)
-    sel = rng.permutation(len(df))[: 4 * 2048].reshape(4, 2048)
-    batches = [torch.from_numpy(np.stack([df.userID.values[s], df.itemID.values[s],
-                                          rng.integers(0, ni, 2048)]).astype(np.int64)).cuda() for s in sel]
-    return m, c, batches, len(df)
-
-
-def alternated(args, runs: dict) -> dict:
-    """ms per iteration of each run in `runs`, their windows alternated: name -> [median, min, max]."""
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for run in runs.values():
-        for _ in range(args.warmup):
-            run()
-    torch.cuda.synchronize()
-    out = {k: [] for k in runs}
-    for _ in range(args.repeats):
-        for k, run in runs.items():
-            e0.record()
-            for _ in range(args.steps):
-                run()
-            e1.record()
-            torch.cuda.synchronize()
-            out[k].append(e0.elapsed_time(e1) / args.steps)
-    return {k: [round(sorted(v)[len(v) // 2], 4), round(min(v), 4), round(max(v), 4)] for k, v in out.items()}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=50, help="iterations per timed window")
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows per variant (median, min, max reported)")
-    ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--scale", type=float, default=1.0, help="shrink the graph (a rehearsal)")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("lgmrec_step_time: needs a GPU (step times are device measurements)")
-    if args.repeats < 5:
-        raise SystemExit("lgmrec_step_time: at least 5 windows")
+    args = parser(steps=50, warmup=10).parse_args()
+    require_gpu("lgmrec_step_time", args)
     from rsx import lgmrec as LG
-    from rsx.trainer import Trainer
 
-    with tempfile.TemporaryDirectory() as root:
-        m, c, batches, n_edges = build(args, root)
+    m, c, batches, n_edges = synth_model("LGMRec", "baby", args, dict(learning_rate=0.001, is_multimodal_model=True),
+                                         (("image_feat_raw.npy", 4096, 5), ("text_feat_raw.npy", 384, 6)))
     m.train()
     d, B, nu, ni, H = m.embedding_dim, 2048, m.n_users, m.n_items, m.hyper_num
     res = {"n_users": nu, "n_items": ni, "train_edges": n_edges, "d": d, "F": [4096, 384], "batch": B,
@@ -196,21 +129,7 @@ def main():
     m.zero_grad(set_to_none=True)
 
     # ---- the step through the Trainer, eager and captured
-    for graph in (False, True):  # the capture last: a failed capture leaves the stream unusable
-        c["rsx_graph_step"] = graph
-        t = Trainer(c, m)
-        k = [0]
-
-        def step(t=t, k=k):
-            t.train_step(batches[k[0] % len(batches)], k[0])
-            k[0] += 1
-
-        try:
-            res.update(alternated(args, {f"step_{'graph' if graph else 'eager'}": step}))
-        except RuntimeError as e:
-            if not graph:
-                raise
-            res["step_graph"] = "not measured: " + str(e).splitlines()[0][:160]
+    res.update(trainer_runs(args, c, m, batches))
     print(json.dumps(res))
 
 

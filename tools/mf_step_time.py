@@ -14,24 +14,18 @@ measured HBM traffic: the BPR working set (tables, moments, scratch: about 55 MB
 of VBPR's stay resident in the 256 MB Infinity Cache between steps.  Needs a GPU: there is no
 CPU fallback for the measured path.
 
-Usage:  python tools/mf_step_time.py [--steps 4000] [--repeats 5] [--warmup 200] [--cpu-steps 3]
+Usage:  python tools/mf_step_time.py [--steps 4000] [--repeats 5] [--warmup 200] [--scale 1.0] [--cpu-steps 3]
                                      [--case NAME] [--no-graph]
 """
 from __future__ import annotations
 
-import argparse
 import json
-import os
-import sys
 import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-for p in (os.path.join(REPO, "recommendar-systems_amd"), os.path.join(REPO, "tests")):
-    sys.path.insert(0, p)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
+from _step_time import parser, require_gpu
 
 HBM_PEAK = 8.0e12
 
@@ -137,19 +131,15 @@ def run_case(name: str, F: int, args, df) -> dict:
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=4000, help="steps per timed window")
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows (median, min, max reported)")
-    ap.add_argument("--warmup", type=int, default=200)
+    ap = parser(steps=4000, warmup=200)
     ap.add_argument("--cpu-steps", type=int, default=3, help="0: skip the CPU restatement")
     ap.add_argument("--case", default=None, help="one of BPR, VBPR_F4480, VBPR_F1536 (default: all)")
     ap.add_argument("--no-graph", action="store_true", help="skip the captured-graph timing (profiler runs)")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("mf_step_time: needs a GPU (step times are device measurements)")
+    require_gpu("mf_step_time")
     from rsx import synth
 
-    df = synth.shaped("sports", seed=0)
+    df = synth.shaped("sports", seed=0, scale=args.scale)
     for name, F in (("BPR", 0), ("VBPR_F4480", 4480), ("VBPR_F1536", 1536)):
         if args.case in (None, name):
             print(json.dumps(run_case(name, F, args, df)), flush=True)

@@ -20,20 +20,13 @@ Usage:  python tools/mgcn_step_time.py [--steps 100] [--repeats 5] [--warmup 20]
 """
 from __future__ import annotations
 
-import argparse
 import json
-import os
-import sys
-import tempfile
 import types
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-sys.path.insert(0, os.path.join(REPO, "recommendar-systems_amd"))
+import torch
+import torch.nn.functional as F
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
+from _step_time import alternated, captured, not_measured, parser, require_gpu, stage_times, synth_model, trainer_step
 
 
 # ------------------------------------------------------------ the comparator blocks
@@ -84,89 +77,18 @@ def block_counts(d: int) -> dict:
             "purify_fwd_bytes_per_gate": 3 * row, "purify_bwd_bytes_per_gate": 5 * row}
 
 
-def build(args, root):
-    from scipy.sparse import coo_matrix
-
-    from rsx import synth
-    from rsx.config import Config
-    from rsx.mgcn import MGCN
-    from rsx.utils import init_seed
-
-    df = synth.shaped("sports", seed=0, scale=args.scale)
-    df = df[df.x_label == 0]
-    nu, ni = int(df.userID.max()) + 1, int(df.itemID.max()) + 1
-    os.makedirs(os.path.join(root, "sports"))
-    np.save(os.path.join(root, "sports", "image_feat.npy"), synth.features(ni, 4096, seed=5))
-    np.save(os.path.join(root, "sports", "text_feat.npy"), synth.features(ni, 384, seed=6))
-    c = Config("MGCN", "sports", dict(data_path=root + "/", train_batch_size=2048, cl_loss=0.01, seed=999,
-                                      is_multimodal_model=True))
-    ds = types.SimpleNamespace(get_user_num=lambda: nu, get_item_num=lambda: ni)
-    loader = types.SimpleNamespace(dataset=ds, inter_matrix=lambda form="coo": coo_matrix(
-        (np.ones(len(df)), (df.userID.values, df.itemID.values)), shape=(nu, ni)))
-    init_seed(999)
-    m = MGCN(c, loader)
-    rng = np.random.default_rng(1)
-    sel = rng.permutation(len(df))[: 4 * 2048].reshape(4, 2048)
-    batches = [torch.from_numpy(np.stack([df.userID.values[s], df.itemID.values[s],
-                                          rng.integers(0, ni, 2048)]).astype(np.int64)).cuda() for s in sel]
-    return m, c, batches
-
-
-class Timer:
-    def __init__(self, args):
-        self.a = args
-
-    def windows(self, run):
-        """ms per iteration of `repeats` windows of `steps` iterations: [median, min, max]."""
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for _ in range(self.a.warmup):
-            run()
-        torch.cuda.synchronize()
-        out = []
-        for _ in range(self.a.repeats):
-            e0.record()
-            for _ in range(self.a.steps):
-                run()
-            e1.record()
-            torch.cuda.synchronize()
-            out.append(e0.elapsed_time(e1) / self.a.steps)
-        out.sort()
-        return [round(out[len(out) // 2], 4), round(out[0], 4), round(out[-1], 4)]
-
-    def graphed(self, run):
-        run()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            run()
-        return self.windows(g.replay)
-
-    def both(self, res, key, run):
-        res[key + "_eager"] = self.windows(run)
-        try:
-            res[key + "_graph"] = self.graphed(run)
-        except RuntimeError as e:  # a torch op that cannot be captured: reported, not hidden
-            res[key + "_graph"] = "not measured: " + str(e).splitlines()[0][:120]
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=100, help="iterations per timed window")
-    ap.add_argument("--repeats", type=int, default=5, help="timed windows (median, min, max reported)")
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--scale", type=float, default=1.0, help="shrink the graph (a rehearsal)")
-    args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("mgcn_step_time: needs a GPU (step times are device measurements)")
+    args = parser(steps=100, warmup=20).parse_args()
+    require_gpu("mgcn_step_time")
     from rsx import mgcn
     from rsx import mgcn_fuse as MF
     from rsx import smore_fuse as SF
     from rsx.blocks import _ego, _Project, ui_backbone
     from rsx.trainer import Trainer
 
-    tm = Timer(args)
-    with tempfile.TemporaryDirectory() as root:
-        m, c, batches = build(args, root)
+    m, c, batches, _ = synth_model("MGCN", "sports", args, dict(cl_loss=0.01, is_multimodal_model=True),
+                                   (("image_feat.npy", 4096, 5), ("text_feat.npy", 384, 6)))
+
     m.train()
     d, B = m.embedding_dim, 2048
     res = {"n_users": m.n_users, "n_items": m.n_items, "d": d, "F": [4096, 384], "batch": B,
@@ -179,27 +101,28 @@ def main():
     for name, blocks in (("fused", MF), ("torch_blocks", torch_blocks)):
         for graph in (False, True):
             mgcn.MF = blocks
-            c["rsx_graph_step"] = graph
-            t = Trainer(c, m)
-            k = [0]
-
-            def step():
-                t.train_step(batches[k[0] % len(batches)], k[0])
-                k[0] += 1
-
+            t, step = trainer_step(c, m, batches, graph)
             key = f"step_{name}_{'graph' if graph else 'eager'}"
             try:
-                res[key] = tm.windows(step)
+                res.update(alternated(args, {key: step}))
             except RuntimeError as e:
                 if name == "fused":
                     raise
-                res[key] = "not measured: " + str(e).splitlines()[0][:120]
+                res[key] = not_measured(e, 120)
                 continue
             if graph:
                 assert t._graph is not None and t._graph.replays >= args.steps
     mgcn.MF = MF
 
     # ---- the two blocks alone, forward + backward on fixed inputs
+    def both(key, run):
+        """`run` launched eagerly and replayed from a graph of its own."""
+        res.update(alternated(args, {key + "_eager": run}))
+        try:
+            res.update(alternated(args, {key + "_graph": captured(run)}))
+        except RuntimeError as e:  # a torch op that cannot be captured: reported, not hidden
+            res[key + "_graph"] = not_measured(e, 120)
+
     g = torch.Generator(device="cuda").manual_seed(3)
     rnd = lambda *s: torch.randn(*s, device="cuda", generator=g) * 0.1  # noqa: E731
     ni, N = m.n_items, m.n_users + m.n_items
@@ -207,8 +130,8 @@ def main():
     go2 = (rnd(ni, d), rnd(ni, d))
     pw = [p for gate in (m.gate_v, m.gate_t) for p in gate.parameters()]
     for name, fn in (("fused", MF.purify), ("torch", torch_purify)):
-        tm.both(res, f"purify_{name}", lambda fn=fn: torch.autograd.grad(fn(fi, ft, item, m.gate_v, m.gate_t),
-                                                                       [item, fi, ft] + pw, go2))
+        both(f"purify_{name}", lambda fn=fn: torch.autograd.grad(fn(fi, ft, item, m.gate_v, m.gate_t),
+                                                                 [item, fi, ft] + pw, go2))
     C_, I_, T_ = (rnd(N, d).requires_grad_() for _ in range(3))
     rows = (batches[0].reshape(-1) + torch.cat([torch.zeros(B, dtype=torch.int64), torch.full((2 * B,), m.n_users)]
                                                ).cuda()).contiguous()
@@ -216,18 +139,17 @@ def main():
         list(m.gate_text_prefer.parameters())
     gr, gf = [rnd(3 * B, d) for _ in range(3)], [rnd(N, d) for _ in range(2)]
     for name, fr, ff in (("fused", MF.fuse_rows, MF.fuse), ("torch", torch_fuse_rows, torch_fuse)):
-        tm.both(res, f"fuse_rows_{name}", lambda fr=fr: torch.autograd.grad(fr(m, C_, I_, T_, rows),
-                                                                          [C_, I_, T_] + fw, gr))
-        tm.both(res, f"fuse_full_{name}", lambda ff=ff: torch.autograd.grad(ff(m, C_, I_, T_), [C_, I_, T_] + fw, gf))
+        both(f"fuse_rows_{name}", lambda fr=fr: torch.autograd.grad(fr(m, C_, I_, T_, rows), [C_, I_, T_] + fw, gr))
+        both(f"fuse_full_{name}", lambda ff=ff: torch.autograd.grad(ff(m, C_, I_, T_), [C_, I_, T_] + fw, gf))
 
     # ---- the whole-step split (eager): device events between the phases
     opt = Trainer(c, m).optimizer
     names = ("proj_fwd", "purify_fwd", "prop_views_fwd", "fuse_fwd", "loss_fwd_bwd", "fuse_bwd", "prop_views_bwd",
              "purify_bwd", "proj_bwd", "adam")
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
-    acc = np.zeros(len(names))
     leaf = lambda *xs: [x.detach().requires_grad_() for x in xs]  # noqa: E731
-    for it in range(args.warmup + args.steps):
+
+    def one_step(it):
         opt.zero_grad(set_to_none=True)
         inter = batches[it % len(batches)]
         ar, trip = m._bidx[B]
@@ -262,12 +184,9 @@ def main():
         ev[9].record()
         opt.step()
         ev[10].record()
-        torch.cuda.synchronize()
-        if it >= args.warmup:
-            acc += [ev[k].elapsed_time(ev[k + 1]) for k in range(len(names))]
-    split = {n: round(float(v) / args.steps, 4) for n, v in zip(names, acc)}
-    split["sum"] = round(float(acc.sum()) / args.steps, 4)
-    res["split_eager_ms"] = split
+        return total
+
+    res["split_eager_ms"], _, total = stage_times(args, names, ev, one_step)
     assert bool(torch.isfinite(total))
     print(json.dumps(res), flush=True)
 
