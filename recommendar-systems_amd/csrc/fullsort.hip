@@ -29,25 +29,15 @@
 
 #include "rsx_common.hpp"
 
-// Profiling ablations (RSX_FS_MODE 1, 4, 5, 6, 8, 9: scores only, pass 1 only, no exact dots,
-// no candidates, candidate counters in out_idx ...) return wrong top-k lists by design: they
-// exist only in an ablation build (tools/build_variant.py fs_abl -DRSX_FS_ABLATION=1).  The
-// product library compiles every FS_ABL(x) to false, and refuses a set RSX_FS_MODE.
-#ifndef RSX_FS_ABLATION
-#define RSX_FS_ABLATION 0
-#endif
-#define FS_ABL(x) (RSX_FS_ABLATION && a.mode == (x))
-
 namespace rsx {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef unsigned long long u64;
 
-#ifndef RSX_FS_CAP
-#define RSX_FS_CAP 256
-#endif
-constexpr int kCap = RSX_FS_CAP;  // candidate slots per (user, chunk) row; compaction when > kCap - 32
+constexpr int kCap = 256;     // candidate slots per (user, chunk) row; compaction when > kCap - 32
 constexpr int kNK = kCap / 64;  // candidate keys per lane while compacting
+constexpr int kSlack = 16;    // running compactions keep up to k + this many keys (compact_slot's slack)
+constexpr int kWarm = 8;      // fs_tiles: tiles scored up front for the warm-up threshold
 constexpr int kMaxK = 96;     // k limit: a chunk's final list (<= k) is <= 2 keys per lane in fs_select
 
 __device__ __forceinline__ unsigned ord_f32(float f) {
@@ -120,7 +110,6 @@ struct FsArgs {
     int* ccount;  // [nb][n_chunks]
     float* out_val;
     int64_t* out_idx;
-    int mode;  // profiling ablation (RSX_FS_MODE, ablation builds only, see FS_ABL): 0 = the product
     const __bf16* Ib;  // fs_screen: bf16 item rows + norm block (kScreenRow), padded to whole 32-item tiles
     int n_lists;       // candidate lists per user: n_chunks (fs_tiles), n_chunks * seg_slots (fs_screen)
     int seg_slots;     // fs_screen: segments per (user block, chunk) (1: unsegmented)
@@ -226,22 +215,10 @@ __device__ __forceinline__ float compact_slot(u64* buf, int n, int k, int lane, 
 // double-buffered register set (lane l: item l&31, floats [h*D/2 + CW*c, +CW)),
 // prefetched one chunk ahead of the MFMAs that consume the current one; rows past
 // the chunk are clamped to a valid row and zeroed, so the load is branch-free.
-#ifndef RSX_FS_FULLLOAD
-#define RSX_FS_FULLLOAD 1
-#endif
-#ifndef RSX_FS_GUARD
-#define RSX_FS_GUARD 1
-#endif
-#ifndef RSX_FS_SLACK
-#define RSX_FS_SLACK 16  // running compactions keep up to k + this many keys (-1: exact top k)
-#endif
-#ifndef RSX_FS_WARM
-#define RSX_FS_WARM 8  // tiles scored up front for the warm-up threshold (0: off)
-#endif
 template <int D, int CW>
 __device__ __forceinline__ void load_chunk(float (&r)[CW], const float* I, int64_t item, int64_t i1, int64_t ni,
                                            int off, bool full = false) {
-    if (RSX_FS_FULLLOAD && full) {  // the whole 32-item tile is inside the chunk (wave-uniform): no clamps, no selects
+    if (full) {  // the whole 32-item tile is inside the chunk (wave-uniform): no clamps, no selects
         const float* p = I + item * D + off;
 #pragma unroll
         for (int q = 0; q < CW / 4; ++q) {
@@ -276,7 +253,7 @@ struct IntC {
 // compaction issue while the other's MFMA chain runs.  Mask cursor and compaction
 // are per-lane / per-user branches; the MFMA chain of tile t is issued before the
 // filter of tile t-1 so the VALU work starts as soon as the previous scores exist.
-template <int D, int MODE>
+template <int D>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? 2 : 1))) void fs_tiles(FsArgs a) {
     constexpr int HALF = D / 2;
     constexpr int CW = HALF < 32 ? HALF : 32;  // floats per operand chunk
@@ -339,7 +316,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? 2 
     int cnt = 0;
     float tau = -INFINITY;
     unsigned omax = 0;  // max ordered score word this lane inserted (the row max is the pair's max)
-    u64 prof[6] = {0, 0, 0, 0, 0, 0};  // MODE 4: memtime per segment (mfma issue, -, filter, compact, mask+copy, tiles)
     const int64_t nsteps = (int64_t)ntiles * NCH;
     float ra[CW], rb[CW];
     if (ntiles > 0) load_chunk<D, CW>(ra, a.I, i0 + j, i1, a.ni, h * HALF, i0 + 32 <= i1);
@@ -362,7 +338,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? 2 
             // next tile's rows (the loads land while this tile is filtered)
 #pragma unroll
             for (int q = 0; q < CW; ++q) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ra[q], bu[q], acc, 0, 0, 0);
-            if (!RSX_FS_GUARD || t + 1 < ntiles)  // the chain has read ra: refill it with the next tile (none after the last)
+            if (t + 1 < ntiles)  // the chain has read ra: refill it with the next tile (none after the last)
                 load_chunk<D, CW>(ra, a.I, i0 + (int64_t)(t + 1) * 32 + j, i1, a.ni, h * HALF,
                                   i0 + (int64_t)(t + 2) * 32 <= i1);
         } else {
@@ -401,7 +377,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? 2 
             m |= ((FULL || ii < rem) && sc > tau) ? (1u << r) : 0u;
         }
         if (!uvalid) m = 0;
-        const u64 ci0 = MODE == 4 ? __builtin_amdgcn_s_memtime() : 0;
         if (__ballot(m != 0u)) {
             // a lane takes ~1 score per tile on average: stage the 16 scores in the
             // lane's LDS scratch and insert only the set bits (per-lane index = address)
@@ -423,16 +398,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? 2 
                 mybuf[pos++] = key;
             }
         }
-        if constexpr (MODE == 4) prof[1] += __builtin_amdgcn_s_memtime() - ci0;
     };
     auto filter = [&](const floatx16& sv, unsigned mb, int64_t tb) __attribute__((always_inline)) {
-        if constexpr (MODE == 1) {
-            float sink = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sink += sv[r];
-            if (sink == 1234.5f) a.out_val[0] = sink;  // keep the MFMAs live
-            return;
-        }
         const bool full = tb + 32 <= i1;
         const bool masked = __ballot(mb != 0u) != 0ull;
         if (full) {
@@ -443,7 +410,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? 2 
         }
     };
     auto compact = [&]() __attribute__((always_inline)) {
-        if constexpr (MODE == 1) return;
         u64 need = __ballot(h == 0 && cnt > kCap - 32);
         while (need) {
             const int jj = __ffsll((long long)need) - 1;
@@ -453,7 +419,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? 2 
             const unsigned hi = max((unsigned)__builtin_amdgcn_readlane((int)omax, jj),
                                     (unsigned)__builtin_amdgcn_readlane((int)omax, jj + 32));
             int kept;
-            const float nt = compact_slot(base + (int64_t)jj * rowstep, n, a.k, lane, &kept, lo, hi, RSX_FS_SLACK);
+            const float nt = compact_slot(base + (int64_t)jj * rowstep, n, a.k, lane, &kept, lo, hi, kSlack);
             if (j == jj) {
                 tau = nt;
                 cnt = kept;
@@ -461,20 +427,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? 2 
         }
     };
 
-    // Warm-up threshold (d <= 64): score the chunk's first RSX_FS_WARM tiles once
+    // Warm-up threshold (d <= 64): score the chunk's first kWarm tiles once
     // without inserting anything, keeping per lane the two largest (masked) scores of
     // each of its 16 accumulator slots -- 64 distinct items per user, so for k <= 64
     // the k-th largest of those scores bounds the chunk's k-th best score from below
     // -- then restart at tile 0 keeping only scores >= that bound.  This replaces the
     // warm-up's unfiltered inserts and every user's first compaction with
-    // RSX_FS_WARM extra tiles of MFMA.
-    if constexpr (NCH == 1 && MODE != 1) {
-        if (RSX_FS_WARM > 0 && ntiles > RSX_FS_WARM && a.k <= 64) {
+    // kWarm extra tiles of MFMA.
+    if constexpr (NCH == 1) {
+        if (ntiles > kWarm && a.k <= 64) {
             const int64_t mp0 = mp, nm0 = next_mask;
             float t1[16], t2[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) t1[r] = t2[r] = -INFINITY;
-            for (int t = 0; t < RSX_FS_WARM; ++t) {
+            for (int t = 0; t < kWarm; ++t) {
                 floatx16 acc;
                 mfma_tile(IntC<0>{}, t, acc);
                 const unsigned mb = mask_bits(i0 + (int64_t)t * 32);
@@ -518,36 +484,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? 2 
         mfma_tile(IntC<0>{}, 0, prev);
         unsigned mb = mask_bits(i0);
         for (int t = 1; t < ntiles; ++t) {
-            const u64 c0 = MODE == 4 ? __builtin_amdgcn_s_memtime() : 0;
             mfma_tile(IntC<0>{}, t, cur);
-            const u64 c1 = MODE == 4 ? __builtin_amdgcn_s_memtime() : 0;
             filter(prev, mb, i0 + (int64_t)(t - 1) * 32);
-            const u64 c2 = MODE == 4 ? __builtin_amdgcn_s_memtime() : 0;
             compact();
-            const u64 c3 = MODE == 4 ? __builtin_amdgcn_s_memtime() : 0;
             mb = mask_bits(i0 + (int64_t)t * 32);
             prev = cur;
-            if constexpr (MODE == 4) {
-                const u64 c4 = __builtin_amdgcn_s_memtime();
-                prof[0] += c1 - c0;
-                prof[2] += c2 - c1;
-                prof[3] += c3 - c2;
-                prof[4] += c4 - c3;
-                prof[5] += 1;
-            }
         }
         filter(prev, mb, i0 + (int64_t)(ntiles - 1) * 32);
         compact();
     }
-    if constexpr (MODE == 4) {
-        if (lane == 0) {
-            unsigned long long* dbg = reinterpret_cast<unsigned long long*>(a.out_idx);
-#pragma unroll
-            for (int q = 0; q < 6; ++q) atomicAdd(dbg + q, (unsigned long long)prof[q]);
-        }
-        return;
-    }
-    if constexpr (MODE == 1) return;
     if (a.n_chunks > 2) {  // lists cut to their top k: fs_select then reads <= k <= 96 keys per chunk
         u64 need = __ballot(h == 0 && cnt > a.k);
         while (need) {
@@ -608,7 +553,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? 2 
 //        has L = -1e10 and needs its masked items in the candidate row (they fill the
 //        top k as -1e10 in index order).  The round-2 "leaner masked-tile branch" that
 //        was reverted skipped masked items in pass 2 and broke exactly this: pass 1 stays
-//        correct, the row misses its -1e10 entries.  Rebuilt (tools/fs_lean_variant.py)
+//        correct, the row misses its -1e10 entries.  Rebuilt
 //        and run on the GPU: it fails the CPU-anchored test on the masked-heavy users only
 //        (rows 1, 2 at every plan, k 50 / 64) and the dense-scores test on its masked-heavy
 //        user at k 50 / 64 only (30 unmasked items: k 1 / 17 need no -1e10 entry); every
@@ -617,10 +562,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? 2 
 //        (tau only rises), and a row is compacted to its exact top k+slack keys before
 //        it could overflow; fs_select then merges the user's lists exactly.
 // Round 3 refinements, each keeping (i)-(v):
-//  * two phases (default; RSX_FS_2PHASE=0: one launch): pass 1 of every segment max-es its
-//    L into a per-user word, pass 2 starts every segment of the user from the largest --
-//    each segment's L is a lower bound of the user's k-th score (iii), so their max is;
-//  * mask-free pass 1 (when every user of the wave has k + m <= 32 * RSX_FS_TOP, m = its
+//  * two phases, one launch each: pass 1 of every segment publishes its samples, fs_thresh
+//    takes the user's L over all of them, pass 2 starts every segment of the user from it --
+//    the segments cover distinct items, so (iii) holds over their union;
+//  * mask-free pass 1 (when every user of the wave has k + m <= 32 * kScreenTop, m = its
 //    masked items in the segment): masked items are sampled by their bounds and L is the
 //    (k + m)-th largest sample -- at most m of the k + m distinct items above it are
 //    masked, so (iii) holds without a per-slot mask select;
@@ -629,20 +574,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? 2 
 //    bound (a masked hit is queued with its mask bit and scored -1e10 at the drain, below
 //    tau); a wave with some tau < -1e10 takes the exact masked select of (iv).
 // ---------------------------------------------------------------------------
-#ifndef RSX_FS_SCREEN_WPE
-#define RSX_FS_SCREEN_WPE 2  // fs_screen waves per SIMD requested at d <= 64
-#endif
-#ifndef RSX_FS_ABUF
-#define RSX_FS_ABUF 2  // fs_screen item-operand buffers at d <= 64 (a ring: loads NB - 1 tiles ahead; 1 at d > 64)
-#endif
-#ifndef RSX_FS_P1PIPE
-#define RSX_FS_P1PIPE 0  // 1: fs_screen pass 1 software-pipelined over two accumulators (A/B variant)
-#endif
-#ifndef RSX_FS_TOP
-#define RSX_FS_TOP 3  // fs_screen pass-1 samples per accumulator slot (2 or 3): 32 * TOP distinct items a user
-#endif
+constexpr int kScreenWpe = 2;  // fs_screen waves per SIMD requested at d <= 64
+constexpr int kScreenTop = 3;  // fs_screen pass-1 samples per accumulator slot: 32 * 3 distinct items a user
+// fs_screen item-operand buffers: a ring of 2 at d <= 64 (loads one tile ahead), 1 at d > 64
 template <int D>
-constexpr int kAbuf = D <= 64 ? RSX_FS_ABUF : 1;
+constexpr int kAbuf = D <= 64 ? 2 : 1;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -702,8 +638,8 @@ __global__ __launch_bounds__(256) void fs_prep(const float* __restrict__ I, int6
     }
 }
 
-// ND exact scores at once (one per candidate, the chains interleaved: each is exact_dot's
-// fmaf chain over d in order, bit for bit; the interleave only hides the FMA latency)
+// ND exact scores <U row, I row> at once (one per candidate, the chains interleaved: each is
+// score_dense's fmaf chain over d in order, bit for bit; the interleave only hides the FMA latency)
 template <int D, int ND>
 __device__ __forceinline__ void exact_dots(const float* const (&u)[ND], const float* const (&v)[ND], float (&out)[ND]) {
     float acc[ND];
@@ -729,36 +665,18 @@ __device__ __forceinline__ void exact_dots(const float* const (&u)[ND], const fl
     for (int n = 0; n < ND; ++n) out[n] = acc[n];
 }
 
-// exact score <U row, I row>: fmaf chain over d in order (as score_dense)
-template <int D>
-__device__ __forceinline__ float exact_dot(const float* __restrict__ u, const float* __restrict__ v) {
-    float acc = 0.f;
-#pragma unroll 4  // blocks of 16 d: the loads of a block in flight together, few registers
-    for (int c = 0; c < D; c += 4) {
-        const float4 x = *reinterpret_cast<const float4*>(u + c), y = ld4(v + c);
-        acc = fmaf(x.x, y.x, acc);
-        acc = fmaf(x.y, y.y, acc);
-        acc = fmaf(x.z, y.z, acc);
-        acc = fmaf(x.w, y.w, acc);
-    }
-    return acc;
-}
-
 // One segment of fs_screen: user block ub, item tiles [ta, tz) of chunk `chunk`, into
 // candidate list `li` of the block's users (lists per user: a.n_lists).
 // train-item mask lists: a user's masked columns of the segment in LDS (up to kMaskCap,
 // stride kMaskCap + 1: conflict-free; screen_segment's LDS form)
-#ifndef RSX_FS_DRAIN
-#define RSX_FS_DRAIN 1  // pass-2 candidates scored per lane per drain (interleaved exact dots; 2: same time)
-#endif
-constexpr int kDrainPer = RSX_FS_DRAIN;
+constexpr int kDrainPer = 1;  // pass-2 candidates scored per lane per drain (interleaved exact dots; 2: same time)
 constexpr int kQueueCap = 64 * kDrainPer + 1024;  // < 64 kDrainPer pending + one tile's (<= 16 per lane)
 constexpr int kMaskCap = 32;
 constexpr int kMaskStride = kMaskCap + 1;
 
-// PH: 0 both passes in one launch (the segment's own L); 1 pass 1 only, the segment's L
-// max-ed into a.lbound[user]; 2 pass 2 only, from tau = the user's a.lbound (every
-// segment of the user: chunks and split ranges)
+// PH: 1 pass 1 only, the segment's samples published to a.samp (fs_thresh takes the user's
+// L over them); 2 pass 2 only, from tau = the user's a.lbound (every segment of the user:
+// chunks and split ranges)
 template <int D, int PH>
 __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int chunk, int li, int ta, int tz,
                                                float* urows, unsigned* queue, int* lcnt, unsigned* lomax,
@@ -791,7 +709,7 @@ __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int 
         const float4 q = uvalid ? ld4(a.U + urow * D + h * HALF + 8 * s + 4) : f4(0.f);
         ss += p.x * p.x + p.y * p.y + p.z * p.z + p.w * p.w + q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
         bu[s] = u32x4{pack_bf16x2(p.x, p.y), pack_bf16x2(p.z, p.w), pack_bf16x2(q.x, q.y), pack_bf16x2(q.z, q.w)};
-        if constexpr (PH != 1) {  // the f32 row for the exact scores (pass 2)
+        if constexpr (PH == 2) {  // the f32 row for the exact scores (pass 2)
             *reinterpret_cast<float4*>(myrow + h * HALF + 8 * s) = p;
             *reinterpret_cast<float4*>(myrow + h * HALF + 8 * s + 4) = q;
         }
@@ -818,12 +736,12 @@ __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int 
         mq = first_ge(mp, hi, i1);
     }
     // m = the user's masked items in [i0, i1).  MASK-FREE pass 1 (wave-uniform, when every
-    // user has k + m <= the 32 * RSX_FS_TOP samples): masked items are sampled by their
+    // user has k + m <= the 32 * kScreenTop samples): masked items are sampled by their
     // bounds like any other, and L is the (k + m)-th largest sample -- of the k + m distinct
     // items at or above it at most m are masked, so k unmasked items score >= L
     const int64_t mcount = mq - mp;
     const int kk = a.k + (int)mcount;
-    const bool mfree = __ballot(uvalid && kk > 32 * RSX_FS_TOP) == 0ull;
+    const bool mfree = __ballot(uvalid && kk > 32 * kScreenTop) == 0ull;
     // The mask cursor, in one of two forms chosen per segment (wave-uniform):
     //  LDS: every user's m <= kMaskCap -- the segment's columns staged once in the user's
     //       LDS list (both lane halves read it; INT_MAX-terminated): the tile loops then
@@ -873,13 +791,14 @@ __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int 
         return mb;
     };
     // A operand: item i0 + 32 t + j, half h (the padded bf16 copy: no clamps), loaded
-    // in tile order through one stepping pointer.  NB > 1: a ring of NB buffers, tile
-    // t's MFMAs preceded by the loads of tile t + NB - 1 (two tiles of latency cover at
+    // in tile order through one stepping pointer.  NB = 2: a ring of two buffers, tile
+    // t's MFMAs preceded by the loads of tile t + 1 (two tiles of latency cover at
     // two waves per SIMD); NB = 1: one buffer refilled with the next tile as soon as the
     // MFMAs have read it.  Every tile issues its load unconditionally (a conditional
     // load would make the compiler's wait before the MFMAs cover the prefetch too): the
-    // last NB - 1 loads read past the segment, into the copy's kScreenPadTiles tiles
+    // last load reads past the segment, into the copy's kScreenPadTiles tiles
     constexpr int NB = kAbuf<D>;
+    static_assert(NB == 1 || NB == 2, "the ring below is written for one or two buffers");
     u32x4 ra[NB][NM + 1];
     const __bf16* const a0 = a.Ib + (i0 + j) * DP;
     const __bf16* anext = a0;
@@ -902,24 +821,21 @@ __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int 
                                                           __builtin_bit_cast(bf16x8, bu[s]), acc, 0, 0, 0);
         if constexpr (NB == 1) load_a(IntC<0>{});
     };
-    // the first NB - 1 tiles' loads, then tiles in groups of NB (ring slots by template)
+    // the first tile's load, then tiles in groups of NB (ring slots by template)
     auto prime = [&]() __attribute__((always_inline)) {
         anext = a0;
         if (ntiles <= 0) return;
         load_a(IntC<0>{});
-        if constexpr (NB > 2) load_a(IntC<1>{});
     };
     auto sweep = [&](auto&& body) __attribute__((always_inline)) {
         for (int t = 0; t < ntiles; t += NB) {
             body(IntC<0>{}, t);
             if constexpr (NB > 1)
                 if (t + 1 < ntiles) body(IntC<1>{}, t + 1);
-            if constexpr (NB > 2)
-                if (t + 2 < ntiles) body(IntC<2>{}, t + 2);
         }
     };
 
-    // pass 1: the RSX_FS_TOP largest lower bounds per slot (t3 unused at 2)
+    // pass 1: the kScreenTop = 3 largest lower bounds per slot
     float t1[16], t2[16], t3[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) t1[r] = t2[r] = t3[r] = -INFINITY;
@@ -952,7 +868,7 @@ __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int 
         // t2 = med3(t1, t2, x), t1 = max(t1, x)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            if constexpr (RSX_FS_TOP == 3) t3[r] = vmed3(t2[r], t3[r], acc[r]);
+            t3[r] = vmed3(t2[r], t3[r], acc[r]);
             t2[r] = vmed3(t1[r], t2[r], acc[r]);
             t1[r] = vmax(t1[r], acc[r]);
         }
@@ -962,121 +878,47 @@ __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int 
         const unsigned mb = p1_issue(form, par, t, acc);
         p1_update(form, t, acc, mb);
     };
-    // Software-pipelined pass 1 (NB <= 2): tile t + 1's MFMAs are issued before tile t's
-    // top-three update, into a second accumulator, so the update's VALU fills the matrix
-    // pipe's dependent-MFMA gaps of the same wave instead of following the chain (one
-    // accumulator serialises MFMA chain -> VALU -> next chain: ~48 VALU per tile behind
-    // 5 dependent MFMAs).  Same tiles, same order of updates: the same samples.
+    // (this sweep software-pipelined over two accumulators: the same time, 0.608-0.613 ms
+    // either way at nb = 35,598, profiles/r04/fs_p1pipe_ab.txt; not adopted)
     auto sweep1 = [&](auto form) __attribute__((always_inline)) {
-        // the mask-free form of the two-phase pass-1 kernel at d <= 64 (the other forms and
-        // kernels would spill past the two-waves-per-SIMD register budget)
-        if constexpr (RSX_FS_P1PIPE && NB <= 2 && decltype(form)::value == 0 && PH == 1 && D <= 64) {
-            if (ntiles <= 0) return;
-            // every tile but the segment's last is full: the loop's tiles take the top-three
-            // update with no masking (one basic block: the next tile's MFMAs and this tile's
-            // VALU interleave, one MFMA per ~9 updates); the last tile the masked form
-            auto upd = [&](floatx16& acc) __attribute__((always_inline)) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    if constexpr (RSX_FS_TOP == 3) t3[r] = vmed3(t2[r], t3[r], acc[r]);
-                    t2[r] = vmed3(t1[r], t2[r], acc[r]);
-                    t1[r] = vmax(t1[r], acc[r]);
-                }
-            };
-#define RSX_P1_INTERLEAVE()                                     \
-    do {                                                        \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      \
-        __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);     \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      \
-        __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);     \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      \
-        __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);     \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      \
-        __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);     \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      \
-        __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);     \
-    } while (0)
-            floatx16 acc0, acc1;
-            unsigned mb0 = p1_issue(form, IntC<0>{}, 0, acc0), mb1 = 0;
-            int t = 0;
-            for (; t + 2 < ntiles; t += 2) {  // tiles t, t + 1 full
-                mb1 = p1_issue(form, IntC<1>{}, t + 1, acc1);
-                upd(acc0);
-                RSX_P1_INTERLEAVE();
-                mb0 = p1_issue(form, IntC<0>{}, t + 2, acc0);
-                upd(acc1);
-                RSX_P1_INTERLEAVE();
-            }
-#undef RSX_P1_INTERLEAVE
-            if (t + 1 < ntiles) {  // tiles t (full) and t + 1 (the last)
-                mb1 = p1_issue(form, IntC<1>{}, t + 1, acc1);
-                upd(acc0);
-                p1_update(form, t + 1, acc1, mb1);
-            } else {
-                p1_update(form, t, acc0, mb0);
-            }
-        } else {
-            sweep([&](auto par, int t) __attribute__((always_inline)) { pass1(form, par, t); });
-        }
+        sweep([&](auto par, int t) __attribute__((always_inline)) { pass1(form, par, t); });
     };
-    unsigned th = 0;
-    if constexpr (PH != 2) {
+    if constexpr (PH == 1) {
         prime();
         if (mfree) sweep1(IntC<0>{});
         else if (mlds_ok) sweep1(IntC<1>{});
         else sweep1(IntC<2>{});
-        if constexpr (PH == 1) {  // publish the samples; fs_thresh takes L over all the user's segments
-            if (uvalid) {
-                // high half of the ordered word (rounding down: a lower bound stays one); -inf
-                // (a missing item) as 0, which counts as no sample
-                auto s16 = [](float x) __attribute__((always_inline)) -> unsigned {
-                    return x == -INFINITY ? 0u : ord_f32(x) >> 16;
-                };
-                uint4* dst = reinterpret_cast<uint4*>(a.samp + ((bslot * a.n_lists + li) * 96 + h * 48));
+        // publish the samples; fs_thresh takes L over all the user's segments
+        if (uvalid) {
+            // high half of the ordered word (rounding down: a lower bound stays one); -inf
+            // (a missing item) as 0, which counts as no sample
+            auto s16 = [](float x) __attribute__((always_inline)) -> unsigned {
+                return x == -INFINITY ? 0u : ord_f32(x) >> 16;
+            };
+            uint4* dst = reinterpret_cast<uint4*>(a.samp + ((bslot * a.n_lists + li) * 96 + h * 48));
 #pragma unroll
-                for (int q = 0; q < 6; ++q) {
-                    unsigned w[4];
+            for (int q = 0; q < 6; ++q) {
+                unsigned w[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int v0 = 8 * q + 2 * e, v1 = v0 + 1;  // sample v: t1 / t2 / t3 [v % 16] by v / 16
-                        const float x0 = v0 < 16 ? t1[v0] : v0 < 32 ? t2[v0 - 16] : t3[v0 - 32];
-                        const float x1 = v1 < 16 ? t1[v1] : v1 < 32 ? t2[v1 - 16] : t3[v1 - 32];
-                        w[e] = s16(RSX_FS_TOP == 3 || v0 < 32 ? x0 : -INFINITY) |
-                               (s16(RSX_FS_TOP == 3 || v1 < 32 ? x1 : -INFINITY) << 16);
-                    }
-                    dst[q] = make_uint4(w[0], w[1], w[2], w[3]);
+                for (int e = 0; e < 4; ++e) {
+                    const int v0 = 8 * q + 2 * e, v1 = v0 + 1;  // sample v: t1 / t2 / t3 [v % 16] by v / 16
+                    const float x0 = v0 < 16 ? t1[v0] : v0 < 32 ? t2[v0 - 16] : t3[v0 - 32];
+                    const float x1 = v1 < 16 ? t1[v1] : v1 < 32 ? t2[v1 - 16] : t3[v1 - 32];
+                    w[e] = s16(x0) | (s16(x1) << 16);
                 }
-                if (h == 0) a.mcnt1[bslot * a.n_lists + li] = (uint16_t)(mfree ? min(mcount, (int64_t)0xfffe) : 0);
+                dst[q] = make_uint4(w[0], w[1], w[2], w[3]);
             }
-            return;
+            if (h == 0) a.mcnt1[bslot * a.n_lists + li] = (uint16_t)(mfree ? min(mcount, (int64_t)0xfffe) : 0);
         }
-        // L = the k-th largest of the lane pair's 32 * RSX_FS_TOP bounds (radix search on
-        // ordered words)
-        for (int bit = 31; bit >= 0; --bit) {
-            const unsigned c = th | (1u << bit);
-            int n = 0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                n += (int)(ord_f32(t1[r]) >= c) + (int)(ord_f32(t2[r]) >= c) +
-                     (RSX_FS_TOP == 3 ? (int)(ord_f32(t3[r]) >= c) : 0);
-            n += __shfl_xor(n, 32, kWave);
-            if (n >= (mfree ? kk : a.k)) th = c;
-        }
-    } else {
-        th = uvalid ? a.lbound[bslot] : 0u;
+        return;
     }
+    const unsigned th = uvalid ? a.lbound[bslot] : 0u;
     // running strict filter "> tau" keeping every score >= L (the ordered word below L's;
     // -0.0 == +0.0 as floats, so a bound that lands on a zero filters with a negative denormal)
     float tau = -INFINITY;
     if (th > ord_f32(-INFINITY)) {
         const float tb = unord_f32(th - 1);
         tau = tb == 0.f ? -__FLT_DENORM_MIN__ : tb;
-    }
-    if (PH == 0 && FS_ABL(5)) {  // profiling ablation: pass 1 only
-        if (uvalid && h == 0) a.ccount[bslot * a.n_lists + li] = 0;
-        if (tau == 1234.5f) a.out_val[0] = tau;
-        __syncthreads();
-        return;
     }
 
     // pass 2: candidates by upper bound go to a queue in LDS (item << 6 | masked << 5 | user);
@@ -1092,7 +934,6 @@ __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int 
         lomax[lane] = 0u;
     }
     int qn = 0;  // queued candidates (wave-uniform)
-    int nq = 0;  // mode 9 (profiling): candidates queued by this segment
     auto compact = [&]() __attribute__((always_inline)) {
         u64 need = __ballot(h == 0 && cnt > kCap - 64 * kDrainPer);  // room for a whole drain group after this
         while (need) {
@@ -1102,7 +943,7 @@ __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int 
             const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)ord_f32(tau), jj);
             const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)omax, jj);
             int kept;
-            const float nt = compact_slot(base + (int64_t)jj * rowstep, nn, a.k, lane, &kept, lo, hi, RSX_FS_SLACK);
+            const float nt = compact_slot(base + (int64_t)jj * rowstep, nn, a.k, lane, &kept, lo, hi, kSlack);
             if (j == jj) {
                 tau = nt;
                 cnt = kept;
@@ -1130,10 +971,7 @@ __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int 
                 up[q] = urows + ju[q] * US;
                 vp[q] = a.I + (int64_t)(e[q] >> 6) * D;
             }
-            if (FS_ABL(6)) {  // profiling ablation: no dots
-#pragma unroll
-                for (int q = 0; q < kDrainPer; ++q) sc[q] = unord_f32(ord_f32(tj[q]) + 1u + (unsigned)lane);
-            } else if (lane < n) {  // (lanes past n hold item 0: valid addresses, results unused)
+            if (lane < n) {  // (lanes past n hold item 0: valid addresses, results unused)
                 exact_dots<D, kDrainPer>(up, vp, sc);
             }
 #pragma unroll
@@ -1174,12 +1012,11 @@ __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int 
         const unsigned ebase = ((unsigned)(tb + 4 * h) << 6) | (unsigned)j;
         // one ballot per slot; its lanes append at queue[qn + their rank] (branch-free tests)
         auto push = [&](bool c, unsigned e) __attribute__((always_inline)) {
-            const u64 bal = __ballot(c) & (FS_ABL(8) ? 0ull : ~0ull);  // 8: profiling ablation, no candidates
+            const u64 bal = __ballot(c);
             if (bal) {
                 const int rk = __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0u));
                 if (c) queue[qn + rk] = e;
                 qn += popc64(bal);
-                if (FS_ABL(9)) nq += popc64(bal);
             }
         };
         const float tv = uvalid ? tau : INFINITY;  // invalid users take nothing
@@ -1225,12 +1062,6 @@ __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int 
         }
     }
     if (uvalid && h == 0) a.ccount[bslot * a.n_lists + li] = cnt;
-    if (FS_ABL(9) && lane == 0) {  // profiling: queued / kept candidate totals into out_idx[0], [1]
-        atomicAdd(reinterpret_cast<unsigned long long*>(a.out_idx), (unsigned long long)nq);
-        int kept = 0;
-        for (int q = 0; q < 32; ++q) kept += lcnt[q];
-        atomicAdd(reinterpret_cast<unsigned long long*>(a.out_idx) + 1, (unsigned long long)kept);
-    }
     __syncthreads();  // LDS reuse by the next segment
 }
 
@@ -1242,7 +1073,7 @@ __device__ __forceinline__ void screen_segment(const FsArgs& a, int64_t ub, int 
 // s of (block, chunk) writes list chunk * S + s (S = a.seg_slots), and the last segment
 // of a (block, chunk) zeroes the counts of the lists after it.
 template <int D, int PH>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? RSX_FS_SCREEN_WPE : 1))) void fs_screen(FsArgs a) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? kScreenWpe : 1))) void fs_screen(FsArgs a) {
     constexpr int US = D + 4;
     __shared__ __attribute__((aligned(16))) float urows[PH == 1 ? 4 : 32 * US];  // pass 2's f32 user rows
     __shared__ unsigned queue[PH == 1 ? 1 : kQueueCap];  // pass 2 candidates
@@ -1274,7 +1105,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(D <= 64 ? RS
         const int64_t wf = ((ub * nt + 1) * nper + T - 1) / T - 1;  // the wave whose range holds tile 0 of ub
         const int seg = a.seg_waves ? (int)(w - wf) : 0;
         screen_segment<D, PH>(a, ub, chunk, chunk * S + seg, t0, t1, urows, queue, lcnt, lomax, mlds);
-        if (PH != 1 && t1 == nt) {  // the block's last segment in this chunk: the later lists are empty
+        if (PH == 2 && t1 == nt) {  // the block's last segment in this chunk: the later lists are empty
             const int j = threadIdx.x & 31;
             const int64_t bslot = ub * 32 + j;
             if (threadIdx.x < 32 && bslot < a.nb)
@@ -1508,8 +1339,7 @@ __global__ __launch_bounds__(256) void fs_select(FsArgs a) {
     }
 }
 
-static void fs_plan(int64_t nb, int64_t ni, int d, int* nw, int* n_chunks, int64_t* chunk_items) {
-    *nw = 1;
+static void fs_plan(int64_t nb, int64_t ni, int d, int* n_chunks, int64_t* chunk_items) {
     const int64_t waves = (nb + 31) / 32;
     // item chunks per 32-user wave: enough waves for two per SIMD (2048 on the chip:
     // one wave's filtering/compaction overlaps the other's MFMA chain), no more
@@ -1518,10 +1348,6 @@ static void fs_plan(int64_t nb, int64_t ni, int d, int* nw, int* n_chunks, int64
     int64_t s = (target + waves - 1) / waves;
     if (s < 1) s = 1;
     if (s > 16) s = 16;
-    {  // tuning override
-        static const int v = env_knob("RSX_FS_CHUNKS", 0, 1, 16);
-        if (v) s = v;
-    }
     int64_t per = (ni + s - 1) / s;
     per = (per + 31) / 32 * 32;
     if (per < 32) per = 32;
@@ -1529,9 +1355,9 @@ static void fs_plan(int64_t nb, int64_t ni, int d, int* nw, int* n_chunks, int64
     *n_chunks = (int)((ni + per - 1) / per);
 }
 
+// fs_screen serves k <= 64; the f32-MFMA fs_tiles path the rest
 static bool fs_use_screen(int k, int d, int64_t ni) {
-    static const int on = env_knob("RSX_FS_SCREEN", 1, 0, 1);  // 0: the f32-MFMA fs_tiles path
-    return on && k <= 64 && (d == 32 || d == 64 || d == 128 || d == 256) && ni < (1ll << 26);  // queue entry: item << 6
+    return k <= 64 && (d == 32 || d == 64 || d == 128 || d == 256) && ni < (1ll << 26);  // queue entry: item << 6
 }
 
 static size_t fs_align(size_t x) { return (x + 255) / 256 * 256; }
@@ -1578,28 +1404,22 @@ static void screen_plan(int64_t nb, int64_t ni, int wps, int* n_chunks, int64_t*
     *n_chunks = (int)((ni + per - 1) / per);
 }
 
-// resident fs_screen waves per SIMD a layout plans for: pass 1 (and the one-launch form)
-// 2 at d <= 128 (register budget), 1 at d = 256; the pass-2 launch of the two-phase form
-// holds no pass-1 samples (fewer registers): RSX_FS_WPS2 (tuning)
-static int fs_wps(int d, int phase) {
-    static const int w2 = env_knob("RSX_FS_WPS2", 0, 1, 4);
-    if (phase == 2 && w2 > 0) return w2;
-    return d <= 128 ? 2 : 1;
-}
+// resident fs_screen waves per SIMD a layout plans for (both passes): 2 at d <= 128
+// (register budget), 1 at d = 256
+static int fs_wps(int d) { return d <= 128 ? 2 : 1; }
 
-static FsLayout fs_layout(int64_t nb, int64_t ni, int k, int d, int wps) {
+static FsLayout fs_layout(int64_t nb, int64_t ni, int k, int d) {
     FsLayout L{};
-    int nw;
+    const int wps = fs_wps(d);
     L.screen = fs_use_screen(k, d, ni);
     if (L.screen) screen_plan(nb, ni, wps, &L.n_chunks, &L.chunk_items);
-    else fs_plan(nb, ni, d, &nw, &L.n_chunks, &L.chunk_items);
+    else fs_plan(nb, ni, d, &L.n_chunks, &L.chunk_items);
     L.n_lists = L.n_chunks;
     L.seg_slots = 1;
     const int64_t n_ub = (nb + 31) / 32;
     const int C = L.n_chunks;
     L.blocks = n_ub * C;
-    static const int seg_env = env_knob("RSX_FS_SEG", 1, 0, 1);  // 0: no balanced split (tuning)
-    if (L.screen && seg_env && (8 % C) == 0) {
+    if (L.screen && (8 % C) == 0) {
         const int64_t slots = (int64_t)fs_cus() * 4 * wps;
         const int64_t wc = slots / C;
         if (n_ub * C > slots && wc >= 1) {
@@ -1623,75 +1443,51 @@ static FsLayout fs_layout(int64_t nb, int64_t ni, int k, int d, int wps) {
     return L;
 }
 
-// workspace: candidate rows | counts | (screen) bf16 item copy
-// candidate lists per user: the pass-2 layout's (two-phase) or the one-launch layout's
-static int fs_lists(int64_t nb, int64_t ni, int k, int d) {
-    return std::max(fs_layout(nb, ni, k, d, fs_wps(d, 1)).n_lists, fs_layout(nb, ni, k, d, fs_wps(d, 2)).n_lists);
-}
-
+// workspace: candidate rows | counts | (screen) bf16 item copy | lbound | samp | mcnt1
 size_t fs_ws(int64_t nb, int64_t ni, int k, int d) {
-    const FsLayout L = fs_layout(nb, ni, k, d, fs_wps(d, 1));
-    const int nl = fs_lists(nb, ni, k, d);
+    const FsLayout L = fs_layout(nb, ni, k, d);
+    const int nl = L.n_lists;
     size_t bytes = fs_align((size_t)nb * nl * kCap * sizeof(u64) + (size_t)nb * nl * sizeof(int) + 512);
     if (L.screen) {
         const size_t ni_pad = (size_t)(ni + 31) / 32 * 32;
         bytes += fs_align((ni_pad + 32 * kScreenPadTiles) * (d + 16) * sizeof(__bf16));
         bytes += fs_align((size_t)nb * sizeof(unsigned));  // lbound
-        bytes += fs_align((size_t)nb * L.n_lists * 96 * sizeof(uint16_t));  // samp (pass-1 layout)
+        bytes += fs_align((size_t)nb * L.n_lists * 96 * sizeof(uint16_t));  // samp
         bytes += fs_align((size_t)nb * L.n_lists * sizeof(uint16_t));       // mcnt1
     }
     return bytes;
 }
 
-// L: the one-launch / pass-1 layout; L2: the pass-2 layout of the two-phase form (its own
-// chunks and segments: pass 1 only publishes per-user thresholds, pass 2 writes the lists)
 template <int D>
-static int launch_fs(FsArgs& a, const FsLayout& L, const FsLayout& L2, hipStream_t s) {
+static int launch_fs(const FsArgs& a, const FsLayout& L, hipStream_t s) {
     const dim3 grid((unsigned)L.blocks);
     if (a.Ib) {  // screened path
         const int64_t ni_pad = (a.ni + 31) / 32 * 32;
         const int64_t nthr = ni_pad * (D / 4);
         hipLaunchKernelGGL((fs_prep<D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, a.I, a.ni, ni_pad,
                            const_cast<__bf16*>(a.Ib));
-        if (FS_ABL(9)) (void)hipMemsetAsync(a.out_idx, 0, 2 * sizeof(int64_t), s);  // profiling counters
-        if (a.lbound) {  // two phases: every segment of a user filters by the user's L over all of them
-            (void)hipMemsetAsync(a.mcnt1, 0xff, (size_t)a.nb * L.n_lists * sizeof(uint16_t), s);
-            hipLaunchKernelGGL((fs_screen<D, 1>), grid, dim3(64), 0, s, a);
-            {
-                const dim3 tg((unsigned)((a.nb + 3) / 4));
-                const uint16_t* sp = a.samp;
-                const uint16_t* mc = a.mcnt1;
-                const int nl = L.n_lists;  // <= 16
-                if (nl <= 4) hipLaunchKernelGGL((fs_thresh<3>), tg, dim3(256), 0, s, sp, mc, nl, a.nb, a.k, a.lbound);
-                else if (nl <= 8) hipLaunchKernelGGL((fs_thresh<6>), tg, dim3(256), 0, s, sp, mc, nl, a.nb, a.k, a.lbound);
-                else hipLaunchKernelGGL((fs_thresh<12>), tg, dim3(256), 0, s, sp, mc, nl, a.nb, a.k, a.lbound);
-            }
-            if (FS_ABL(5)) return last_rc();
-            a.n_chunks = L2.n_chunks;
-            a.chunk_items = L2.chunk_items;
-            a.n_lists = L2.n_lists;
-            a.seg_slots = L2.seg_slots;
-            a.seg_waves = L2.seg_waves;
-            hipLaunchKernelGGL((fs_screen<D, 2>), dim3((unsigned)L2.blocks), dim3(64), 0, s, a);
-        } else {
-            hipLaunchKernelGGL((fs_screen<D, 0>), grid, dim3(64), 0, s, a);
+        // two phases: every segment of a user filters by the user's L over all of them
+        (void)hipMemsetAsync(a.mcnt1, 0xff, (size_t)a.nb * L.n_lists * sizeof(uint16_t), s);
+        hipLaunchKernelGGL((fs_screen<D, 1>), grid, dim3(64), 0, s, a);
+        {
+            const dim3 tg((unsigned)((a.nb + 3) / 4));
+            const uint16_t* sp = a.samp;
+            const uint16_t* mc = a.mcnt1;
+            const int nl = L.n_lists;  // <= 16
+            if (nl <= 4) hipLaunchKernelGGL((fs_thresh<3>), tg, dim3(256), 0, s, sp, mc, nl, a.nb, a.k, a.lbound);
+            else if (nl <= 8) hipLaunchKernelGGL((fs_thresh<6>), tg, dim3(256), 0, s, sp, mc, nl, a.nb, a.k, a.lbound);
+            else hipLaunchKernelGGL((fs_thresh<12>), tg, dim3(256), 0, s, sp, mc, nl, a.nb, a.k, a.lbound);
         }
-    } else if (FS_ABL(4)) {
-        hipLaunchKernelGGL((fs_tiles<D, 4>), grid, dim3(64), 0, s, a);
-    } else if (FS_ABL(1)) {
-        hipLaunchKernelGGL((fs_tiles<D, 1>), grid, dim3(64), 0, s, a);
+        hipLaunchKernelGGL((fs_screen<D, 2>), grid, dim3(64), 0, s, a);
     } else {
-        hipLaunchKernelGGL((fs_tiles<D, 0>), grid, dim3(64), 0, s, a);
+        hipLaunchKernelGGL((fs_tiles<D>), grid, dim3(64), 0, s, a);
     }
     const dim3 sg((unsigned)((a.nb + 3) / 4));
-    if (FS_ABL(9)) return last_rc();  // profiling: out_idx holds the candidate counts
-    if (a.Ib || !RSX_FS_ABLATION || a.mode == 0) {
-        const int n = a.n_lists;
-        if (n <= 2) hipLaunchKernelGGL((fs_select<2>), sg, dim3(256), 0, s, a);
-        else if (n <= 4) hipLaunchKernelGGL((fs_select<4>), sg, dim3(256), 0, s, a);
-        else if (n <= 8) hipLaunchKernelGGL((fs_select<8>), sg, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((fs_select<16>), sg, dim3(256), 0, s, a);
-    }
+    const int n = a.n_lists;
+    if (n <= 2) hipLaunchKernelGGL((fs_select<2>), sg, dim3(256), 0, s, a);
+    else if (n <= 4) hipLaunchKernelGGL((fs_select<4>), sg, dim3(256), 0, s, a);
+    else if (n <= 8) hipLaunchKernelGGL((fs_select<8>), sg, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((fs_select<16>), sg, dim3(256), 0, s, a);
     return last_rc();
 }
 
@@ -1704,8 +1500,8 @@ int fs_call(const float* U, const int64_t* users, int64_t nb, const float* I, in
     if (nb == 0) return RSX_OK;
     if (!ws || ws_bytes < fs_ws(nb, ni, k, d)) return RSX_ERR_WORKSPACE;
     FsArgs a;
-    const FsLayout L = fs_layout(nb, ni, k, d, fs_wps(d, 1));
-    const int nl = fs_lists(nb, ni, k, d);
+    const FsLayout L = fs_layout(nb, ni, k, d);
+    const int nl = L.n_lists;
     a.n_chunks = L.n_chunks;
     a.chunk_items = L.chunk_items;
     a.n_lists = L.n_lists;
@@ -1731,29 +1527,18 @@ int fs_call(const float* U, const int64_t* users, int64_t nb, const float* I, in
         char* p = static_cast<char*>(ws) + fs_align((size_t)nb * nl * kCap * sizeof(u64) + (size_t)nb * nl * sizeof(int) + 512);
         a.Ib = reinterpret_cast<const __bf16*>(p);
         const size_t ni_pad = (size_t)(ni + 31) / 32 * 32;
-        static const int two = env_knob("RSX_FS_2PHASE", 1, 0, 1);  // 0: both passes in one launch, per-segment thresholds
         char* q = p + fs_align((ni_pad + 32 * kScreenPadTiles) * (d + 16) * sizeof(__bf16));
-        a.lbound = two ? reinterpret_cast<unsigned*>(q) : nullptr;
+        a.lbound = reinterpret_cast<unsigned*>(q);
         q += fs_align((size_t)nb * sizeof(unsigned));
         a.samp = reinterpret_cast<uint16_t*>(q);
         q += fs_align((size_t)nb * L.n_lists * 96 * sizeof(uint16_t));
         a.mcnt1 = reinterpret_cast<uint16_t*>(q);
     }
-    {
-        static const int mode = env_knob("RSX_FS_MODE", 0, 0, 9);
-        if (mode != 0 && !RSX_FS_ABLATION) {
-            fprintf(stderr, "librsx: RSX_FS_MODE=%d is a profiling ablation (wrong top-k by design); it runs only in "
-                            "an ablation build (tools/build_variant.py NAME -DRSX_FS_ABLATION=1)\n", mode);
-            return RSX_ERR_UNSUPPORTED;
-        }
-        a.mode = mode;
-    }
-    const FsLayout L2 = a.lbound ? fs_layout(nb, ni, k, d, fs_wps(d, 2)) : L;
     switch (d) {
-        case 32: return launch_fs<32>(a, L, L2, s);
-        case 64: return launch_fs<64>(a, L, L2, s);
-        case 128: return launch_fs<128>(a, L, L2, s);
-        case 256: return launch_fs<256>(a, L, L2, s);
+        case 32: return launch_fs<32>(a, L, s);
+        case 64: return launch_fs<64>(a, L, s);
+        case 128: return launch_fs<128>(a, L, s);
+        case 256: return launch_fs<256>(a, L, s);
         default: return RSX_ERR_UNSUPPORTED;
     }
 }
@@ -1810,7 +1595,7 @@ size_t rsx_fullsort_ws_bytes(int64_t n_batch, int64_t n_items, int32_t k) {
 
 int rsx_fullsort_plan(int64_t n_batch, int64_t n_items, int32_t d, int32_t* n_chunks, int64_t* chunk_items) {
     if (!n_chunks || !chunk_items || n_batch < 0 || n_items <= 0) return RSX_ERR_ARG;
-    const rsx::FsLayout L = rsx::fs_layout(n_batch, n_items, 50, d, rsx::fs_wps(d, 1));  // the plan of k <= 64 calls (pass 1)
+    const rsx::FsLayout L = rsx::fs_layout(n_batch, n_items, 50, d);  // the plan of k <= 64 calls
     *n_chunks = L.n_chunks;
     *chunk_items = L.chunk_items;
     return RSX_OK;

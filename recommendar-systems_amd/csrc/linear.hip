@@ -20,13 +20,6 @@ namespace rsx {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-// RSX_LBWD_ABL (timing ablations of the fused backward, tools/build_variant.py only; the
-// product build leaves it 0): 1 skips the dx products, 2 skips the dW products, 3 drops the
-// sched_group_barrier orderings (the compiler's schedule; results unchanged)
-#ifndef RSX_LBWD_ABL
-#define RSX_LBWD_ABL 0
-#endif
-
 constexpr int kWgChunk = 16;         // rows per wave step: 8 MFMA k-steps of 2 rows
 constexpr int kWgTargetWaves = 2048; // two per SIMD (LDS-staged blocks interleave)
 
@@ -43,8 +36,6 @@ struct WgPlan {
     int splits;    // S
     int slots() const { return splits * rw; }
 };
-
-static int lin_env(const char* name, int dflt) { return env_knob(name, dflt, 1, 1 << 20); }
 
 // in_dim: a multiple of 4 (float4 rows); the i tiles cover ceil(in_dim / 32) * 32 columns and
 // the kernel masks the columns past in_dim (loads as zeros, no stores)
@@ -245,20 +236,16 @@ __device__ __forceinline__ void wgrad_partial_body(int64_t bid, const float* __r
 #pragma unroll
             for (int q = 0; q < IG; ++q) bv[u][q] = xb[(2 * u + h) * XP + 32 * q];
         }
-        if (!(DX && RSX_LBWD_ABL == 2)) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u)
+        for (int u = 0; u < 8; ++u)
 #pragma unroll
-                for (int q = 0; q < IG; ++q)
-                    acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u][q], acc[q], 0, 0, 0);
-        }
+            for (int q = 0; q < IG; ++q)
+                acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u], bv[u][q], acc[q], 0, 0, 0);
         // every LDS operand read issued before the first MFMA (one latency per step, not
         // one per MFMA pair)
-#if RSX_LBWD_ABL != 3
         __builtin_amdgcn_sched_group_barrier(0x100, 8 + 8 * IG, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 8 * IG, 0);
-#endif
-        if constexpr (DX && RSX_LBWD_ABL != 1) {
+        if constexpr (DX) {
             if (db_blk) {
 #pragma unroll
                 for (int u = 0; u < 8; ++u) dbacc += av[u];
@@ -294,10 +281,8 @@ __device__ __forceinline__ void wgrad_partial_body(int64_t bid, const float* __r
                     d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(A4[k].z, B4[k].z, d0, 0, 0, 0);
                     d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(A4[k].w, B4[k].w, d1, 0, 0, 0);
                 }
-#if RSX_LBWD_ABL != 3
                 __builtin_amdgcn_sched_group_barrier(0x100, 2 * K4, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 4 * K4, 0);
-#endif
                 const floatx4_t d = d0 + d1;
                 // lane holds columns 4 q4 .. 4 q4 + 3 of the tile, row n16
                 const int64_t row = c0 + mt * 16 + n16;
@@ -478,20 +463,13 @@ extern "C" size_t rsx_linear_wgrad_ws_bytes(int64_t n, int32_t out_dim, int32_t 
     return (size_t)p.slots() * (size_t)out_dim * (size_t)in_dim * sizeof(float);
 }
 
-// the fused backward stages a W slice too: IC <= 64 keeps two blocks per CU in LDS
-// (RSX_LBWD_IG / RSX_LBWD_WAVES: tuning overrides)
-static int bwd_ig() {
-    static const int v = lin_env("RSX_LBWD_IG", 2);
-    return v;
-}
-static int64_t bwd_waves() {
-    static const int v = lin_env("RSX_LBWD_WAVES", kWgTargetWaves);
-    return v;
-}
+// the fused backward stages a W slice too: IC <= 64 (two i tiles a wave) keeps two blocks
+// per CU in LDS (1 and 4 tiles, 1,024 and 3,072 target waves: profiles/r03/final2/lbwd/)
+constexpr int kBwdIg = 2;
 
 extern "C" size_t rsx_linear_bwd_ws_bytes(int64_t n, int32_t out_dim, int32_t in_dim) {
     if (n <= 0 || (out_dim != 32 && out_dim != 64 && out_dim != 128) || in_dim <= 0 || (in_dim % 4)) return 0;
-    const WgPlan p = wg_plan(n, out_dim, in_dim, bwd_ig(), bwd_waves());
+    const WgPlan p = wg_plan(n, out_dim, in_dim, kBwdIg);
     return (size_t)p.slots() * ((size_t)out_dim * (size_t)in_dim + (size_t)out_dim) * sizeof(float);
 }
 
@@ -513,7 +491,7 @@ extern "C" int rsx_linear_bwd(const float* g, const float* x, const float* W, in
         return last_rc();
     }
     if (ws_bytes < rsx_linear_bwd_ws_bytes(n, out_dim, in_dim) || !ws) return RSX_ERR_WORKSPACE;
-    const WgPlan p = wg_plan(n, out_dim, in_dim, bwd_ig(), bwd_waves());
+    const WgPlan p = wg_plan(n, out_dim, in_dim, kBwdIg);
     if (p.nob != 1) return RSX_ERR_UNSUPPORTED;
     float* part = static_cast<float*>(ws);
     const dim3 grid((unsigned)(p.nob * p.nib * p.splits));
@@ -523,10 +501,7 @@ extern "C" int rsx_linear_bwd(const float* g, const float* x, const float* W, in
                        p.rows, p.nob, p.nib, part, W, dx, do_db)
     const int key = p.ig * 8 + p.otb;
     switch (key) {
-        case 4 * 8 + 4: RSX_WGX(4, 4); break;
-        case 4 * 8 + 2: RSX_WGX(4, 2); break;
-        case 4 * 8 + 1: RSX_WGX(4, 1); break;
-        case 2 * 8 + 4: RSX_WGX(2, 4); break;
+        case 2 * 8 + 4: RSX_WGX(2, 4); break;  // (p.ig <= kBwdIg)
         case 2 * 8 + 2: RSX_WGX(2, 2); break;
         case 2 * 8 + 1: RSX_WGX(2, 1); break;
         case 1 * 8 + 4: RSX_WGX(1, 4); break;
@@ -549,10 +524,10 @@ extern "C" int rsx_linear_bwd(const float* g, const float* x, const float* W, in
 // the pair's plans: the 2048-wave budget split by input width (the blocks of both problems
 // then carry about the same rows x columns each, so they finish together)
 static void pair_plans(int64_t n, int32_t out_dim, int32_t in0, int32_t in1, WgPlan& p0, WgPlan& p1) {
-    const int64_t w = bwd_waves();
+    const int64_t w = kWgTargetWaves;
     const int64_t w0 = std::max<int64_t>(4, w * in0 / (in0 + in1)), w1 = std::max<int64_t>(4, w - w0);
-    p0 = wg_plan(n, out_dim, in0, bwd_ig(), w0);
-    p1 = wg_plan(n, out_dim, in1, bwd_ig(), w1);
+    p0 = wg_plan(n, out_dim, in0, kBwdIg, w0);
+    p1 = wg_plan(n, out_dim, in1, kBwdIg, w1);
 }
 
 extern "C" size_t rsx_linear_bwd_pair_ws_bytes(int64_t n, int32_t out_dim, int32_t in0, int32_t in1) {
@@ -590,10 +565,7 @@ extern "C" int rsx_linear_bwd_pair(const float* g0, const float* x0, const float
     const dim3 grid((unsigned)(nb0 + nb1));
 #define RSX_WGP(IG, OTB) hipLaunchKernelGGL((wgrad_partial_pair<IG, OTB>), grid, dim3(256), 0, s, a, b, nb0, n, (int)out_dim)
     switch (p0.ig * 8 + p0.otb) {
-        case 4 * 8 + 4: RSX_WGP(4, 4); break;
-        case 4 * 8 + 2: RSX_WGP(4, 2); break;
-        case 4 * 8 + 1: RSX_WGP(4, 1); break;
-        case 2 * 8 + 4: RSX_WGP(2, 4); break;
+        case 2 * 8 + 4: RSX_WGP(2, 4); break;  // (p.ig <= kBwdIg)
         case 2 * 8 + 2: RSX_WGP(2, 2); break;
         case 2 * 8 + 1: RSX_WGP(2, 1); break;
         case 1 * 8 + 4: RSX_WGP(1, 4); break;

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(256) void smore_proj(SpecProjArgs a) {
 // features: the d = 64 block's LDS footprint (37 KB instead of 55 KB: four blocks a CU, not
 // two), so twice the waves hide the K-chunk loads.  The two halves of a pair are blocks
 // b and b + 8 (the same XCD under the round-robin deal): the X chunks come from its L2 for
-// the second.  Same products in the same K order: the results are smore_proj<128>'s bits.
+// the second.  Same products in the same K order: the results are the whole block's (proj_block<128>) bits.
 // Grid: 16 * ceil(nb / 8) for nb = tiles * (S0 + S1); blocks past nb exit.
 template <int D>
 __global__ __launch_bounds__(256) void smore_proj_half(SpecProjArgs a, int nb) {
@@ -844,10 +844,8 @@ extern "C" size_t rsx_smore_spectral_spec_floats(int64_t n_items, int32_t d) {
 // (C5's 768-wide features: one split; two -- 1,440 blocks in 2.8 rounds of the 512 resident
 // d = 128 blocks instead of 720 in 1.4 -- measured no faster once smore_spec_fwd sums them:
 // proj 148.7 -> 138.3 us, spec_fwd 73.6 -> 82.5)
-static int env_int(const char* name, int dflt) { return env_knob(name, dflt, 1, 1 << 20); }
-
 static int proj_splits(int64_t n, int K) {
-    static const int target = env_int("RSX_PROJ_TARGET", 1536), mink = env_int("RSX_PROJ_MINK", 512);
+    constexpr int target = 1536, mink = 512;
     const int64_t tiles = (n + kPjItems - 1) / kPjItems;
     int64_t s = (target + 2 * tiles - 1) / (2 * tiles);  // blocks per modality ~target (C3: 3.37 -> 3.31 ms/step at 1536 vs 512)
     const int64_t smax = K / mink > 0 ? K / mink : 1;
@@ -929,10 +927,8 @@ extern "C" int rsx_smore_spectral_fwd(const float* V, int32_t dv, const float* W
         hipLaunchKernelGGL(smore_proj<64>, gp, dim3(256), 0, s, p);
         hipLaunchKernelGGL(smore_spec_fwd<64>, gs, dim3(256), 0, s, a);
     } else {
-        static const int half = env_knob("RSX_PROJ_HALF", 1, 0, 1);  // 0: one block per (tile, split) (A/B)
         const int nb = (int)(p.tiles * (p.S[0] + p.S[1]));
-        if (half) hipLaunchKernelGGL(smore_proj_half<128>, dim3((unsigned)(16 * ((nb + 7) / 8))), dim3(256), 0, s, p, nb);
-        else hipLaunchKernelGGL(smore_proj<128>, gp, dim3(256), 0, s, p);
+        hipLaunchKernelGGL(smore_proj_half<128>, dim3((unsigned)(16 * ((nb + 7) / 8))), dim3(256), 0, s, p, nb);
         hipLaunchKernelGGL(smore_spec_fwd<128>, gs, dim3(256), 0, s, a);
     }
     return last_rc();

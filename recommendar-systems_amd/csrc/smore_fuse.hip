@@ -301,18 +301,10 @@ constexpr int kOccC0 = 0, kOccC3 = 1, kOccC4 = 2, kOccF0 = 3, kOccF1 = 4, kOccF2
 // the table row of logical row r (r < 0: none)
 __device__ __forceinline__ int64_t src_row(const PrefArgs& a, int64_t r) { return (r >= 0 && a.rows) ? a.rows[r] : r; }
 
-// Y[row] += x (float atomics: rows repeat within a batch).  RSX_PREF_PLAIN_STORES=1 (a timing
-// variant only, tools/build_variant.py: wrong where rows repeat) stores instead, to price the atomics.
-#ifndef RSX_PREF_PLAIN_STORES
-#define RSX_PREF_PLAIN_STORES 0
-#endif
+// Y[row] += x (float atomics: rows repeat within a batch)
 template <int D>
 __device__ __forceinline__ void fatomic(float* Y, int64_t row, int g, const Fld<D>& x) {
     if (row < 0 || !Y) return;
-    if (RSX_PREF_PLAIN_STORES) {
-        fstore<D>(Y, row, g, x);
-        return;
-    }
 #pragma unroll
     for (int t = 0; t < D / 16; ++t)
 #pragma unroll
@@ -668,16 +660,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void p
 // made every wave a chain of ~n / 64 dependent round trips).  The row ids come from
 // `RowAt`: the global int64 array, or (pref_segsum_lds) the block's int32 copy in LDS.
 constexpr int kSegList = 128;  // a wave's occurrence list (LDS int32)
-#ifndef RSX_SEGSUM_UB
-#define RSX_SEGSUM_UB 0  // 0: 8 occurrences a round at d = 64, 4 at d = 128 (16 at d = 64 spilled: 4x slower)
-#endif
-// RSX_SEGSUM_ABL (timing ablations, tools/build_variant.py only): 1 skips the occurrence
-// loads of pref_segsum_plan, 2 its table stores
-#ifndef RSX_SEGSUM_ABL
-#define RSX_SEGSUM_ABL 0
-#endif
+// occurrences summed per round: 8 at d = 64, 4 at d = 128 (16 at d = 64 spilled: 4x slower)
 template <int D>
-constexpr int kSegUB = RSX_SEGSUM_UB ? RSX_SEGSUM_UB : (D <= 64 ? 8 : 4);  // occurrences summed per round
+constexpr int kSegUB = D <= 64 ? 8 : 4;
 template <int D, typename RowAt>
 __device__ __forceinline__ void segsum_one(int64_t j, int64_t n, RowAt row_at, const float* __restrict__ occ,
                                            float* __restrict__ gC, float* __restrict__ gIE, float* __restrict__ gTE,
@@ -854,11 +839,6 @@ __global__ __launch_bounds__(256) void pref_segsum_plan(const int64_t* __restric
 #pragma unroll
             for (int p = 0; p < PL; ++p) {
                 const int64_t q = 64 * p;
-                if (RSX_SEGSUM_ABL == 1) {
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[t][u][p] = (float)k;
-                    continue;
-                }
                 v[t][0][p] = o[kOccC0 * sl + q];
                 v[t][1][p] = o[kOccC3 * sl + q];
                 v[t][2][p] = o[kOccC4 * sl + q];
@@ -882,7 +862,6 @@ __global__ __launch_bounds__(256) void pref_segsum_plan(const int64_t* __restric
         }
     }
     const int64_t x = rows[j];
-    if (RSX_SEGSUM_ABL == 2 && aC[0] != 12345.f) return;
 #pragma unroll
     for (int p = 0; p < PL; ++p) {
         const int64_t col = x * D + lane + 64 * p;
@@ -1407,11 +1386,12 @@ __global__ __launch_bounds__(64 * kNceWaves) void nce_bwd(NceArgs a) {
 // The same products in the same K grouping and order as nce_bwd; the waves' partials are
 // summed in wave order through LDS (transposed back to the row layout) and the epilogue
 // is nce_bwd's.
-template <int D, int NG>
+template <int D>
 __global__ __launch_bounds__(64 * kNceWaves) void nce_bwd_t(NceArgs a) {
     // NG own 16-row groups per block: every other-view tile a wave loads feeds NG groups'
-    // MFMAs (NG = 2 halves the L2 reads of the other view's tiles; same K split over the
-    // waves, same order, so the results are NG = 1's bit for bit)
+    // MFMAs (two halve the L2 reads of the other view's tiles; same K split over the
+    // waves, same order, so the results are one group's bit for bit)
+    constexpr int NG = 2;
     constexpr int T = D / 16;
     // The partials' tile red[w][row][col] is stored with row r's columns rotated by 8 sig(r)
     // floats (sig below).  Unrotated, the epilogue's ds_read_b128 of row c, columns 16 t + 4 g
@@ -1920,12 +1900,11 @@ int rsx_smore_gates_saved(int32_t backward, const float* const* conv, const floa
     // one gate per block row, except the mul-mode backward (its g_item needs all three
     // sigmoids of a row: one block runs the three gates)
     a.nbx = ((n + 15) / 16 + 3) / 4;
-    // blocks: the row blocks, at most RSX_GATE_BLOCKS (default: 2 per CU -- the LDS
-    // weight copy allows two; each block then strides over its row blocks)
+    // blocks: the row blocks, at most 2 per CU (the LDS weight copy allows two; each
+    // block then strides over its row blocks)
     const unsigned gy = (backward && mul) ? 1u : 3u;
-    static const int64_t cap_env = env_knob("RSX_GATE_BLOCKS", 0, 1, 1 << 20);
     int64_t gx = a.nbx;
-    const int64_t cap = cap_env > 0 ? cap_env : (int64_t)(2 * device_cus()) / gy;
+    const int64_t cap = (int64_t)(2 * device_cus()) / gy;
     if (cap > 0 && gx > cap) gx = cap;
     const dim3 grid((unsigned)gx, gy);
     hipStream_t s = as_stream(stream);
@@ -1977,13 +1956,6 @@ int rsx_tag_rows(int32_t* row_tag, const int64_t* rows, int64_t n, const int32_t
     hipLaunchKernelGGL(sf::tag_rows_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), row_tag,
                        rows, n, tag_dev);
     return last_rc();
-}
-
-// RSX_SEGSUM_GLOBAL=1: the per-row sums read the row ids from global memory even when
-// they fit the LDS copy (timing A/B; the two kernels give identical results)
-static bool seg_global() {
-    static const bool v = env_knob("RSX_SEGSUM_GLOBAL", 0, 0, 1) != 0;
-    return v;
 }
 
 int rsx_smore_pref_rows(int32_t backward, const float* const* W, const float* const* b, const float* content,
@@ -2089,7 +2061,7 @@ int rsx_smore_pref_rows_saved(int32_t backward, const float* const* W, const flo
             const dim3 sg((unsigned)((n + 3) / 4));
             if (d == 64) hipLaunchKernelGGL(sf::pref_segsum_plan<64>, sg, dim3(256), 0, s, rows, n, plan, occ, g_content, g_image, g_text, g_fusion);
             else hipLaunchKernelGGL(sf::pref_segsum_plan<128>, sg, dim3(256), 0, s, rows, n, plan, occ, g_content, g_image, g_text, g_fusion);
-        } else if (n <= sf::kSegLds && !seg_global()) {  // row ids < 2^31 (table rows)
+        } else if (n <= sf::kSegLds) {  // row ids < 2^31 (table rows)
             const dim3 sg((unsigned)((n + sf::kSegWaves - 1) / sf::kSegWaves)), sb(64 * sf::kSegWaves);
             if (d == 64) hipLaunchKernelGGL(sf::pref_segsum_lds<64>, sg, sb, 0, s, rows, n, occ, g_content, g_image, g_text, g_fusion);
             else hipLaunchKernelGGL(sf::pref_segsum_lds<128>, sg, sb, 0, s, rows, n, occ, g_content, g_image, g_text, g_fusion);
@@ -2178,8 +2150,7 @@ static int nce_setup(sf::NceArgs& a, const float* side, const float* content, co
     a.ttl = a.norms + 4 * batch;
     a.lrow = a.ttl + 2 * batch;
     a.E = batch <= sf::kNceStoreMax ? a.lrow + 2 * batch : nullptr;
-    static const int t64 = env_knob("RSX_NCE_T64", 1, 0, 1);
-    a.nrmT = a.E && (d == 128 || t64) ? a.E + 2 * batch * batch : nullptr;  // read by nce_bwd_t only
+    a.nrmT = a.E ? a.E + 2 * batch * batch : nullptr;  // read by nce_bwd_t only
     return RSX_OK;
 }
 
@@ -2264,17 +2235,13 @@ int rsx_smore_loss_rows_bwd(const float* side_c, const float* content_c, const i
 }
 
 static int nce_bwd_launch(sf::NceArgs& a, int64_t batch, int32_t d, hipStream_t s) {
-    const dim3 grid((unsigned)((batch + 15) / 16), 2, 2);
-    if (a.E && a.nrmT) {  // the forward's exp tiles and transposed rows (same workspace, same batch);
-        // d = 64 too since round 6 (its reduction tile conflict-free: C3's backward 81 -> 54 us;
-        // RSX_NCE_T64=0 keeps nce_bwd<64> there, the round-5 form, for A/B)
-        static const int ng = env_knob("RSX_NCE_GROUPS", 2, 1, 2);
-        const dim3 g2((unsigned)((batch + 31) / 32), 2, 2);
-        if (d == 128 && ng == 2) hipLaunchKernelGGL((sf::nce_bwd_t<128, 2>), g2, dim3(64 * sf::kNceWaves), 0, s, a);
-        else if (d == 128) hipLaunchKernelGGL((sf::nce_bwd_t<128, 1>), grid, dim3(64 * sf::kNceWaves), 0, s, a);
-        else if (ng == 2) hipLaunchKernelGGL((sf::nce_bwd_t<64, 2>), g2, dim3(64 * sf::kNceWaves), 0, s, a);
-        else hipLaunchKernelGGL((sf::nce_bwd_t<64, 1>), grid, dim3(64 * sf::kNceWaves), 0, s, a);
-    } else {
+    if (a.E) {  // the forward's exp tiles and transposed rows (same workspace, same batch);
+        // d = 64 too since round 6 (its reduction tile conflict-free: C3's backward 81 -> 54 us)
+        const dim3 g2((unsigned)((batch + 31) / 32), 2, 2);  // two own 16-row groups a block
+        if (d == 128) hipLaunchKernelGGL(sf::nce_bwd_t<128>, g2, dim3(64 * sf::kNceWaves), 0, s, a);
+        else hipLaunchKernelGGL(sf::nce_bwd_t<64>, g2, dim3(64 * sf::kNceWaves), 0, s, a);
+    } else {  // batches above kNceStoreMax: no stored tiles, the exps recomputed
+        const dim3 grid((unsigned)((batch + 15) / 16), 2, 2);
         if (d == 64) hipLaunchKernelGGL(sf::nce_bwd<64>, grid, dim3(64 * sf::kNceWaves), 0, s, a);
         else hipLaunchKernelGGL(sf::nce_bwd<128>, grid, dim3(64 * sf::kNceWaves), 0, s, a);
     }

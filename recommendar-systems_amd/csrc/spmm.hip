@@ -24,20 +24,11 @@ namespace rsx {
 // ---------------------------------------------------------------------------
 // row epilogues
 // ---------------------------------------------------------------------------
-// RSX_ADAM_LATE=1 (since round 6): the ADAM epilogue loads p, m, v after the gathers rather
-// than before them (102 instead of 115 VGPRs; the C2 ADAM launch 32.4-33.1 against
-// 33.3-33.4 us in six alternating runs, profiles/r06/spmm_occ/)
-#ifndef RSX_ADAM_LATE
-#define RSX_ADAM_LATE 1
-#endif
-// RSX_FINAL_LATE (A/B): the FINAL epilogue's four stored layers loaded after the gathers
-#ifndef RSX_FINAL_LATE
-#define RSX_FINAL_LATE 0
-#endif
-
 // Row operands of an epilogue, loaded by epi_load right after the work item is
-// known so that they are in flight during the neighbour gathers (the ADAM kind
-// reads five rows: a whole extra dependent memory trip if loaded after the loop).
+// known so that they are in flight during the neighbour gathers.  The ADAM kind's
+// p, m, v are the exception: the epilogue loads them after the gathers (102 instead
+// of 115 VGPRs; the C2 ADAM launch 32.4-33.1 against 33.3-33.4 us in six alternating
+// runs, profiles/r06/spmm_occ/).
 struct EpiIn {
     float4 a, b, c, d, e;
     float w;
@@ -64,23 +55,16 @@ __device__ __forceinline__ EpiIn epi_load(const rsx_epilogue& e, int64_t row, in
     if constexpr (KIND == RSX_EPI_LAYERSUM || KIND == RSX_EPI_AXPBY) {
         if (s_in) in.a = ld4(s_in + off);
     } else if constexpr (KIND == RSX_EPI_FINAL) {
-        if (!RSX_FINAL_LATE) {
-            if (s_in) in.a = ld4(s_in + off);
-            if (r_add) in.b = ld4(r_add + off);
-            if (e.aux) in.c = ld4(e.aux + off);
-            if (e.e0) in.d = ld4(e.e0 + off);
-        }
+        if (s_in) in.a = ld4(s_in + off);
+        if (r_add) in.b = ld4(r_add + off);
+        if (e.aux) in.c = ld4(e.aux + off);
+        if (e.e0) in.d = ld4(e.e0 + off);
     } else if constexpr (KIND == RSX_EPI_ADD) {
         if (s_in) in.a = ld4(s_in + off);
         if (r_add) in.b = ld4(r_add + off);
     } else if constexpr (KIND == RSX_EPI_ADAM) {
         if (s_in) in.a = ld4(s_in + off);
         if (r_add) in.b = ld4(r_add + off);
-        if (!RSX_ADAM_LATE) {
-            in.c = ld4(e.p + off);
-            in.d = ld4(e.m + off);
-            in.e = ld4(e.v + off);
-        }
         if (e.reg_cnt && (!(tf & RSX_TAG_SPARSE_R) || in.tagged)) {
             const int32_t* c = e.reg_cnt + 3 * row;
             in.regc = (float)c[0] * e.reg_k[0] + (float)c[1] * e.reg_k[1] + (float)c[2] * e.reg_k[2];
@@ -136,20 +120,10 @@ __device__ __forceinline__ void epilogue(const rsx_epilogue& e, int64_t row, flo
         st4(e.s_out + off, s);
     } else if constexpr (KIND == RSX_EPI_FINAL) {
         // (((s_in + r_add) + aux) + e0) + acc: the stored layers summed in layer order
-        float4 a4 = in.a, b4 = in.b, c4 = in.c, d4 = in.d;
-        if (RSX_FINAL_LATE) {  // epi_load's operands, loaded here (the same rows, the same tag rules)
-            const int tf = tag_flags(e);
-            const float* s_in = (!(tf & RSX_TAG_SPARSE_S) || in.tagged) ? e.s_in : nullptr;
-            const float* r_add = (!(tf & RSX_TAG_SPARSE_R) || in.tagged) ? e.r_add : nullptr;
-            a4 = s_in ? ld4(s_in + off) : f4(0.f);
-            b4 = r_add ? ld4(r_add + off) : f4(0.f);
-            c4 = e.aux ? ld4(e.aux + off) : f4(0.f);
-            d4 = e.e0 ? ld4(e.e0 + off) : f4(0.f);
-        }
-        float4 t = a4;
-        if (e.r_add) t = add4(t, b4);
-        if (e.aux) t = add4(t, c4);
-        if (e.e0) t = add4(t, d4);
+        float4 t = in.a;
+        if (e.r_add) t = add4(t, in.b);
+        if (e.aux) t = add4(t, in.c);
+        if (e.e0) t = add4(t, in.d);
         const float4 s = (e.s_in || e.r_add || e.aux || e.e0) ? add4(t, acc) : acc;
         st4(e.f + off, mul4(e.beta, s));
     } else if constexpr (KIND == RSX_EPI_AXPBY) {
@@ -174,12 +148,8 @@ __device__ __forceinline__ void epilogue(const rsx_epilogue& e, int64_t row, flo
         }
         st4(e.y + off, mul4(e.beta, s));
     } else if constexpr (KIND == RSX_EPI_ADAM) {
-        float4 p = in.c, m = in.d, v = in.e;
-        if (RSX_ADAM_LATE) {  // moments loaded after the gathers (fewer registers live across them)
-            p = ld4(e.p + off);
-            m = ld4(e.m + off);
-            v = ld4(e.v + off);
-        }
+        // moments loaded here, after the gathers (fewer registers live across them)
+        float4 p = ld4(e.p + off), m = ld4(e.m + off), v = ld4(e.v + off);
         float4 g = e.s_in ? add4(in.a, acc) : acc;
         g = mul4(e.beta, g);
         if (e.reg_cnt) g = add4(g, mul4(in.regc, p));  // sum over occurrences of k * ego row
@@ -357,37 +327,6 @@ __device__ __forceinline__ void bcast8(int cm, int vi, int* c, float* v) {
     c[7] = row_bcast<8 * H + 7>(cm); v[7] = __int_as_float(row_bcast<8 * H + 7>(vi));
 }
 
-// all 16 entries of the row at once: 16 neighbour loads in flight per lane
-__device__ __forceinline__ float4 gather16(float4 acc, int cm, float vm, int n, const float* xl) {
-    const int vi = __float_as_int(vm);
-    int c[16];
-    float v[16];
-    bcast8<0>(cm, vi, c, v);
-    bcast8<1>(cm, vi, c + 8, v + 8);
-    float4 xv[16];
-#pragma unroll
-    for (int t = 0; t < 16; ++t) xv[t] = (t < n && c[t] >= 0) ? ld4(xl + (int64_t)c[t] * 64) : f4(0.f);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) acc = fma4(v[t], xv[t], acc);
-    return acc;
-}
-
-#ifndef RSX_SPMM_G16
-#define RSX_SPMM_G16 0
-#endif
-#ifndef RSX_SPMM_WAVES
-#define RSX_SPMM_WAVES 0
-#endif
-#if RSX_SPMM_WAVES
-#define RSX_SPMM_ATTR __attribute__((amdgpu_waves_per_eu(RSX_SPMM_WAVES, RSX_SPMM_WAVES)))
-#else
-#define RSX_SPMM_ATTR
-#endif
-// RSX_ADAM_WAVES (tuning): the minimum waves a SIMD for the ADAM kind alone
-#ifndef RSX_ADAM_WAVES
-#define RSX_ADAM_WAVES 0
-#endif
-
 // One group of G lanes per work item {row, slot, begin, end}.
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -397,15 +336,6 @@ __device__ __forceinline__ void st4_sc1(float* p, float4 v) {
     const v4f t = {v.x, v.y, v.z, v.w};
     asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(t) : "memory");
 }
-
-#ifndef RSX_SPMM_PF
-#define RSX_SPMM_PF 1
-#endif
-// d >= 128: (col, val) loaded 16 entries per lane-row and DPP-broadcast (0: the
-// per-entry wave-uniform loads; a compile-time A/B switch, tools/build_variant.py)
-#ifndef RSX_SPMM_WIDE_BCAST
-#define RSX_SPMM_WIDE_BCAST 1
-#endif
 
 // (col, val) of the next work item's first 16 nonzeros, loaded while the current
 // item's first gathers are in flight (d = 64): the next item starts with its
@@ -454,7 +384,7 @@ __device__ __forceinline__ void spmm_item(const rsx_csr& a, const float* __restr
             const bool mine = j + li < end;
             int cm;
             float vm;
-            if (RSX_SPMM_PF && j == wk.z && have_pf) {
+            if (j == wk.z && have_pf) {
                 cm = mine ? pf.cm : 0;
                 vm = mine ? pf.vm : 0.f;
             } else {
@@ -463,10 +393,6 @@ __device__ __forceinline__ void spmm_item(const rsx_csr& a, const float* __restr
             }
             if (sparse_x && mine && xtag[cm] != tag_of(e)) cm = -1;  // zero X row: no gather
             const int n = end - j;
-#if RSX_SPMM_G16
-            acc = gather16(acc, cm, vm, n, xl);
-#else
-#if RSX_SPMM_PF
             if (j == wk.z && has_nxt) {
                 // issue this chunk's first 8 gathers, then the next item's (col, val), then add
                 const int vi = __float_as_int(vm);
@@ -485,19 +411,15 @@ __device__ __forceinline__ void spmm_item(const rsx_csr& a, const float* __restr
             } else {
                 acc = gather8<0>(acc, cm, vm, n, xl);
             }
-#else
-            acc = gather8<0>(acc, cm, vm, n, xl);
-#endif
             if (n > 8) acc = gather8<1>(acc, cm, vm, n, xl);
-#endif
         }
-    } else if constexpr (RSX_SPMM_WIDE_BCAST && D >= 128) {
+    } else if constexpr (D >= 128) {
         // d = 128 / 256: a group spans 2 / 4 DPP rows.  Lane li loads entry j + (li & 15):
         // the rows of a group load the same 16 (col, val) entries (one coalesced request
         // each), and row_newbcast:t hands entry t to every lane of its row -- two vector
         // loads per 16 nonzeros instead of two wave-uniform loads per nonzero, so the
         // memory pipe carries the neighbour-row gathers only.  Same fma chain in nonzero
-        // order as the per-entry loop below: bit-identical results.
+        // order as the per-entry loop below (d = 32): bit-identical results.
         const int q = li & 15;
         for (; j < end; j += 16) {
             const bool mine = j + q < end;
@@ -570,10 +492,9 @@ __device__ __forceinline__ void spmm_main_body(const rsx_csr& a, const float* __
 // (the next descriptor is loaded before the current item is processed); blocks
 // [n_main, n_main + n_long) are the long rows' fixups (fix_only: every block is one).
 template <int D, int KIND>
-__global__ RSX_SPMM_ATTR __launch_bounds__(kBlock)
-__attribute__((amdgpu_waves_per_eu(KIND == RSX_EPI_ADAM && RSX_ADAM_WAVES ? RSX_ADAM_WAVES : 1))) void spmm_main(rsx_csr a, const float* __restrict__ x,
-                                                                  rsx_epilogue e, float* __restrict__ slab,
-                                                                  int64_t n_main, int fix_only, TagJob tj) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1))) void spmm_main(
+    rsx_csr a, const float* __restrict__ x, rsx_epilogue e, float* __restrict__ slab, int64_t n_main, int fix_only,
+    TagJob tj) {
     constexpr int G = D / 4;
     constexpr int GPB = kBlock / G;
     const int li = threadIdx.x % G;
@@ -694,16 +615,8 @@ __global__ __launch_bounds__(kBlock) void rowwise_kernel(int64_t n_rows, rsx_epi
 // than one 2,048-block round gets 1,536 longer-lived blocks (C2 step 133.6-135.0 us
 // against 135.8-137.8 at 2,048 and 152 at 1,024; its ADAM layer 33.5 vs 35.2-35.9
 // us), while a list that fits one round launches whole (baby: 111 us/step whole,
-// 115 capped at 1,536; tools/gpu/maxb_sweep.sh, ab_legs.sh).  RSX_SPMM_MAXB
-// overrides (tuning), RSX_SPMM_MAXB_ADAM for the Adam-epilogue kind alone.
-static int64_t env_blocks(const char* name) { return env_knob(name, 0, 1, 1 << 20); }
-static int64_t spmm_max_blocks(int kind, int d, int64_t n) {
-    static const int64_t all = env_blocks("RSX_SPMM_MAXB");
-    static const int64_t adam = env_blocks("RSX_SPMM_MAXB_ADAM");
-    if (kind == RSX_EPI_ADAM && adam > 0) return adam;
-    if (all > 0) return all;
-    return d <= 64 && n > 2048 ? 1536 : 2048;
-}
+// 115 capped at 1,536; profiles/r02/maxb/).
+static int64_t spmm_max_blocks(int d, int64_t n) { return d <= 64 && n > 2048 ? 1536 : 2048; }
 
 // Fixup blocks ride in the same launch only while they cannot fill the chip (so
 // the partials' blocks always find room whatever the dispatch order); beyond that
@@ -715,7 +628,7 @@ static int launch_spmm(const rsx_csr& a, const float* x, const rsx_epilogue& e, 
                        hipStream_t s, const TagJob& tj) {
     constexpr int GPB = kBlock / (D / 4);
     int64_t n_main = (a.n_work + GPB - 1) / GPB;
-    n_main = std::min(n_main, spmm_max_blocks(KIND, D, n_main));
+    n_main = std::min(n_main, spmm_max_blocks(D, n_main));
     const bool inl = a.n_long <= kInlineFixups;
     const int64_t n_tag = tj.batch > 0 ? (3 * tj.batch + kBlock - 1) / kBlock : 0;
     const int64_t nb = n_main + (inl ? a.n_long : 0) + n_tag;
@@ -734,7 +647,7 @@ static int launch_batch(SpmmBatch& b, hipStream_t s) {
     int64_t nm = 0, nf = 0;
     for (int p = 0; p < b.count; ++p) {
         int64_t n_main = (b.a[p].n_work + GPB - 1) / GPB;
-        n_main = std::min(n_main, spmm_max_blocks(KIND, D, n_main));
+        n_main = std::min(n_main, spmm_max_blocks(D, n_main));
         b.n_main[p] = n_main;
         b.main_off[p] = nm;
         b.fix_off[p] = nf;

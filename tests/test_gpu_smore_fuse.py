@@ -460,7 +460,10 @@ def _infonce_ref(v1, v2, tau):
 
 
 @pytest.mark.parametrize("d,B,nu,ni", [(64, 2048, 19445, 7050), (128, 2048, 3000, 2000), (64, 1000, 500, 300),
-                                       (64, 17, 40, 30)])
+                                       (64, 17, 40, 30),
+                                       # B = 4097: the smallest batch above the stored-exp cap (nce_bwd, the
+                                       # recompute form)
+                                       (64, 4097, 500, 300), (128, 4097, 500, 300)])
 def test_infonce2_vs_torch(cuda, d, B, nu, ni):
     from rsx import smore_fuse as SF
 

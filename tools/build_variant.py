@@ -1,7 +1,7 @@
-"""Build a variant of librsx.so with extra flags (-D..., -mllvm ...) on every source into
-rsx/lib/variants/<name>/
-(for side-by-side timing on the GPU box via RSX_LIB=...).
-usage: python tools/build_variant.py NAME -DFOO=1 [-DBAR=2 ...]"""
+"""Build a variant of librsx.so with extra compiler flags (-mllvm ..., -O..., -f...) on every
+source into rsx/lib/variants/<name>/ (for side-by-side timing on the GPU box via RSX_LIB=...).
+The sources read no -D switch of their own: a variant differs by code generation only.
+usage: python tools/build_variant.py NAME FLAG [FLAG ...]"""
 import os
 import subprocess
 import sys

@@ -1,8 +1,7 @@
-"""The InfoNCE pair's backward (rsx_smore_infonce_bwd_scaled: nce_bwd_t<128, NG>) at the C5
-batch (B = 2048, d = 128) timed alone, and a digest of its gradients: run it once per
-RSX_NCE_GROUPS value (the knob is read once per process) and compare the digests (the two
-forms sum the same products in the same order, so the digests must match).
-Usage: RSX_NCE_GROUPS=1|2 python tools/gpu/micro_nce.py"""
+"""The InfoNCE pair's backward (rsx_smore_infonce_bwd_scaled: nce_bwd_t<128>) at the C5
+batch (B = 2048, d = 128) timed alone, and a digest of its gradients (the products are
+summed in a fixed order, so the digest is the same from run to run and build to build).
+Usage: python tools/gpu/micro_nce.py"""
 import hashlib
 import os
 import sys
@@ -60,7 +59,7 @@ def main():
     fe.record()
     torch.cuda.synchronize()
     t = (s.elapsed_time(e) - fill.elapsed_time(fe)) / reps * 1e3
-    print(f"infonce bwd B={B} d={d} groups={os.environ.get('RSX_NCE_GROUPS', '2')}: {t:.1f} us "
+    print(f"infonce bwd B={B} d={d}: {t:.1f} us "
           f"(zero fills subtracted), digest {digest}", flush=True)
 
 

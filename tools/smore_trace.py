@@ -1,9 +1,9 @@
-"""Per-step kernel breakdown of a SMORE bench trace (tools/gpu/r06_smoretrace.sh output):
+"""Per-step kernel breakdown of a SMORE bench trace (a rocprofv3 --kernel-trace run of bench.py):
 steps are delimited by the step's second adam_multi (the mirror-gradient step runs two);
 prints, for step STEP (default: the last whole timed one), each kernel's total time in
 the step, its count, and the step's GPU busy time vs wall time.
 
-python tools/smore_trace.py gpurun_out/r06strace/c3_trace_min.csv [STEP]"""
+python tools/smore_trace.py KERNEL_TRACE.csv [STEP]"""
 import collections
 import csv
 import sys
