@@ -1626,6 +1626,98 @@ int rsx_lgm_loss_fwd(const rsx_lgm_loss_args* a, float* out, void* ws, size_t ws
 int rsx_lgm_loss_bwd(const rsx_lgm_loss_args* a, const float* go, float* gC, float* gMv, float* gMt, float* gGv,
                      float* gGt, void* ws, size_t ws_bytes, rsx_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* MMGCN: modal-GCN layers, the wide product, normalise, loss (mmgcn.hip)     */
+/* ------------------------------------------------------------------------ */
+/*
+ * One modal-GCN layer of width d (reference src/models/mmgcn.py:176-186, the concatenating
+ * branch; leaky = leaky_relu with slope 0.01), on a = A_hat x (the caller's SpMM):
+ *   h = leaky(a Wc)            Wc [d, d] as [in, out] (BaseModel.weight)
+ *   u = leaky(x Wl^T + bl)     Wl [d, d] (nn.Linear layout)
+ *   out = leaky([h | u + E] Wg^T + bg)      Wg [d, 2 d]
+ * rsx_mmgcn_layer_fwd writes h, u, out [n, d] in one launch.  rsx_mmgcn_layer_bwd, given
+ * g_out and the forward's out, h, u (slopes are read off their signs), writes in one launch
+ *   go = g_out .* slope(out), gh = (go Wg[:, :d]) .* slope(h), gu = (go Wg[:, d:]) .* slope(u)
+ *   (the pre-activation gradient rows: dWg = go^T [h | xh], dbg = colsum go, dWl = gu^T x,
+ *   dbl = colsum gu, dWc = a^T gh: rsx_smore_wgrad), xh = u + E, g_a = gh Wc^T and
+ *   g_x = gu Wl (the caller adds A_hat^T g_a).
+ * d in {64, 128}, else RSX_ERR_UNSUPPORTED; every pointer 16-byte aligned; n = 0 is RSX_OK.
+ * Caller-owned buffers, no allocation or synchronisation; stream-ordered, graph-capturable.
+ */
+int rsx_mmgcn_layer_fwd(const float* a, const float* x, const float* E, const float* Wc, const float* Wl,
+                        const float* bl, const float* Wg, const float* bg, int64_t n, int32_t d, float* h, float* u,
+                        float* out, rsx_stream_t stream);
+int rsx_mmgcn_layer_bwd(const float* g_out, const float* out, const float* h, const float* u, const float* E,
+                        const float* Wc, const float* Wl, const float* Wg, int64_t n, int32_t d, float* go, float* gh,
+                        float* gu, float* xh, float* g_a, float* g_x, rsx_stream_t stream);
+/*
+ * The wide product of layer 1 and of the image MLP, and its data gradient:
+ *   P = (X .* slope(mx)) op(B) + bias        X = [x0 (k0 columns, row stride ld0) | x1 (k1, ld1)]
+ *   V = act ? leaky(P) : P;  V = V .* slope(my);  y = V;  y2 = V + r
+ * slope(t) = 1 where t > 0, else 0.01 (t a saved leaky output).  mx [n, k0] (row stride ldmx;
+ * needs k1 = 0), xm_out [n, k0] receives the masked X (a weight gradient's rows), my, r, y, y2
+ * [n, n_out] contiguous; any of mx, xm_out, bias, my, r and one of y, y2 may be NULL (y2 without
+ * r is V).  B is [K, n_out] (b_kn = 1) or [n_out, K] (b_kn = 0), K = k0 + k1, row stride ldb:
+ * a column block of a wider weight is given by its first element and the weight's stride.
+ * The data gradient of Y = leaky(X W^T + b) is the same call with x0 = dY, mx = Y, B = W and
+ * b_kn = 1.  n_out a multiple of 32; k0, k1 and the strides multiples of 4 (a ragged last
+ * 32-wide slab is masked); every pointer 16-byte aligned; else RSX_ERR_UNSUPPORTED / _ARG.
+ * f32 MFMA, one fixed summation order: deterministic.
+ */
+typedef struct rsx_mmgcn_gemm_args {
+    const float* x0;
+    const float* x1;
+    const float* mx;
+    float* xm_out;
+    const float* B;
+    const float* bias;
+    const float* my;
+    const float* r;
+    float* y;
+    float* y2;
+    int64_t n, ld0, ld1, ldmx, ldb;
+    int32_t k0, k1, n_out, b_kn, act, pad0;
+} rsx_mmgcn_gemm_args;
+int rsx_mmgcn_gemm(const rsx_mmgcn_gemm_args* a, rsx_stream_t stream);
+/*
+ * F.normalize over the rows of x [n, w] (mmgcn.py:168): y = x / max(|x|_2, 1e-12), den[row] the
+ * divisor (y may be x); and torch's backward from y and den: (g - y <g, y>) / den, or g / den on a
+ * row whose norm was clamped (no gradient passes through the clamp).  w a multiple of 4.
+ */
+int rsx_mmgcn_normalize_fwd(const float* x, int64_t n, int32_t w, float* y, float* den, rsx_stream_t stream);
+int rsx_mmgcn_normalize_bwd(const float* gy, const float* y, const float* den, int64_t n, int32_t w, float* gx,
+                            rsx_stream_t stream);
+/* out[n_cols] = the column sums of g [n, n_cols] (a bias gradient): partial sums over blocks of
+ * 128 rows, added in block order (deterministic). */
+size_t rsx_mmgcn_colsum_ws_bytes(int64_t n, int32_t n_cols);
+int rsx_mmgcn_colsum(const float* g, int64_t n, int32_t n_cols, float* out, void* ws, size_t ws_bytes,
+                     rsx_stream_t stream);
+/*
+ * MMGCN's loss (mmgcn.py:79-97) on the modality tables xv, xt [n_users + n_items, d] (either
+ * may be NULL: num_modal = the number given) and the constant id table E.  With
+ * rep = (xv + xt) / num_modal and x_b = <rep_u, rep_p> - <rep_u, rep_n>:
+ *   out = {bpr + reg, bpr, reg},  bpr = mean softplus(-x_b),
+ *   reg = reg_weight (sum_b (2 |E_u|^2 + |E_p|^2 + |E_n|^2) / (2 batch d) + pref_term)
+ * (pref_term: the caller's constant mean(preference_v^2); reg has no gradient).  With `result`
+ * non-NULL the forward also writes result = rep over the whole table.  rsx_mmgcn_loss_bwd
+ * writes EVERY row of g [n_users + n_items, d], the gradient of either modality table (the two
+ * are equal), zero off the batch, repeated rows summed by the first-occurrence walk
+ * (deterministic).  d in {64, 128}, batch <= 65536, n_users + n_items < 2^31.
+ */
+typedef struct rsx_mmgcn_loss_args {
+    const float *xv, *xt, *E;
+    const int64_t* triplets; /* [3, batch] users, positives, negatives (item ids, not offset) */
+    int64_t n_users, n_items, batch;
+    int32_t d;
+    float reg_weight, pref_term;
+    int32_t pad0;
+} rsx_mmgcn_loss_args;
+size_t rsx_mmgcn_loss_ws_bytes(int64_t batch, int32_t d);
+int rsx_mmgcn_loss_fwd(const rsx_mmgcn_loss_args* a, float* out, float* result, void* ws, size_t ws_bytes,
+                       rsx_stream_t stream);
+int rsx_mmgcn_loss_bwd(const rsx_mmgcn_loss_args* a, const float* go, float* g, void* ws, size_t ws_bytes,
+                       rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,17 @@ class LgmLossArgs(C.Structure):
                 ("n_items", I64), ("batch", I64), ("d", I32), ("alpha", F32), ("reg", F32), ("pad0", I32)]
 
 
+class MmgcnGemmArgs(C.Structure):
+    _fields_ = [("x0", P), ("x1", P), ("mx", P), ("xm_out", P), ("B", P), ("bias", P), ("my", P), ("r", P), ("y", P),
+                ("y2", P), ("n", I64), ("ld0", I64), ("ld1", I64), ("ldmx", I64), ("ldb", I64), ("k0", I32),
+                ("k1", I32), ("n_out", I32), ("b_kn", I32), ("act", I32), ("pad0", I32)]
+
+
+class MmgcnLossArgs(C.Structure):
+    _fields_ = [("xv", P), ("xt", P), ("E", P), ("triplets", P), ("n_users", I64), ("n_items", I64), ("batch", I64),
+                ("d", I32), ("reg_weight", F32), ("pref_term", F32), ("pad0", I32)]
+
+
 class LatticeGraph(C.Structure):
     _fields_ = [("n", I64), ("k", I32), ("n_mod", I32), ("f", I32), ("lam", F32), ("F", P * 2), ("idx", P * 2),
                 ("oidx", P * 2), ("oval", P * 2), ("modal_weight", P), ("w", P), ("invn", P * 2), ("a", P * 2),
@@ -294,6 +305,16 @@ def _declare(lib):
         "rsx_lgm_loss_ws_bytes": (C.c_size_t, [I64, I32]),
         "rsx_lgm_loss_fwd": (C.c_int, [C.POINTER(LgmLossArgs), P, P, C.c_size_t, P]),
         "rsx_lgm_loss_bwd": (C.c_int, [C.POINTER(LgmLossArgs), P, P, P, P, P, P, P, C.c_size_t, P]),
+        "rsx_mmgcn_layer_fwd": (C.c_int, [P, P, P, P, P, P, P, P, I64, I32, P, P, P, P]),
+        "rsx_mmgcn_layer_bwd": (C.c_int, [P, P, P, P, P, P, P, P, I64, I32, P, P, P, P, P, P, P]),
+        "rsx_mmgcn_gemm": (C.c_int, [C.POINTER(MmgcnGemmArgs), P]),
+        "rsx_mmgcn_normalize_fwd": (C.c_int, [P, I64, I32, P, P, P]),
+        "rsx_mmgcn_normalize_bwd": (C.c_int, [P, P, P, I64, I32, P, P]),
+        "rsx_mmgcn_colsum_ws_bytes": (C.c_size_t, [I64, I32]),
+        "rsx_mmgcn_colsum": (C.c_int, [P, I64, I32, P, P, C.c_size_t, P]),
+        "rsx_mmgcn_loss_ws_bytes": (C.c_size_t, [I64, I32]),
+        "rsx_mmgcn_loss_fwd": (C.c_int, [C.POINTER(MmgcnLossArgs), P, P, P, C.c_size_t, P]),
+        "rsx_mmgcn_loss_bwd": (C.c_int, [C.POINTER(MmgcnLossArgs), P, P, P, C.c_size_t, P]),
         "rsx_cpu_spmm": (C.c_int, [P, P, P, I64, P, I32, P]),
         "rsx_cpu_propagate_mean": (C.c_int, [P, P, P, I64, P, I32, I32, P]),
         "rsx_cpu_layergcn_forward": (C.c_int, [P, P, P, I64, P, I32, I32, P, P, P]),
@@ -338,6 +359,9 @@ EXPORTED = ["rsx_version", "rsx_csr_schedule_host", "rsx_csr_schedule_rebind", "
             "rsx_lgm_ssl_ws_bytes", "rsx_lgm_ssl_fwd", "rsx_lgm_ssl_bwd", "rsx_lgm_assign_fwd", "rsx_lgm_assign_bwd", "rsx_lgm_gumbel_of_bits",
             "rsx_lgm_hgnn_ws_bytes", "rsx_lgm_hgnn_reduce", "rsx_lgm_hgnn_expand", "rsx_lgm_hgnn_rowdots",
             "rsx_lgm_loss_ws_bytes", "rsx_lgm_loss_fwd", "rsx_lgm_loss_bwd",
+            "rsx_mmgcn_layer_fwd", "rsx_mmgcn_layer_bwd", "rsx_mmgcn_gemm", "rsx_mmgcn_normalize_fwd",
+            "rsx_mmgcn_normalize_bwd", "rsx_mmgcn_colsum_ws_bytes", "rsx_mmgcn_colsum", "rsx_mmgcn_loss_ws_bytes",
+            "rsx_mmgcn_loss_fwd", "rsx_mmgcn_loss_bwd",
             "rsx_cpu_spmm", "rsx_cpu_propagate_mean", "rsx_cpu_layergcn_forward", "rsx_cpu_layergcn_backward",
             "rsx_cpu_bpr", "rsx_cpu_fullsort_topk", "rsx_cpu_adam", "rsx_cpu_gcn_step_ws_floats", "rsx_cpu_gcn_step"]
 

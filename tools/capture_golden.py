@@ -13,13 +13,13 @@ modifies a reference file:
    `src/models/mgcn.py:59,69`, `src/models/lattice.py:76,87`);
 4. `torch_scatter.scatter_add` is restated with `index_add_` (`src/utils/utils.py:140`).
 
-GRCN adds a fifth for its own capture: `torch_geometric` as far as `src/models/grcn.py` uses it
-(`_install_pyg_shim`).
+GRCN and MMGCN add a fifth for their own captures: `torch_geometric` as far as `src/models/grcn.py`
+and `src/models/mmgcn.py` use it (`_install_pyg_shim`).
 
 Outputs are small `.npz` files under `tests/golden/` (data only: inputs and the
 reference's outputs). The reference itself never travels to the GPU box.
 
-Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn]
+Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn]
 """
 from __future__ import annotations
 
@@ -1062,23 +1062,30 @@ GRCN_ROWS = dict(rep=8, grad=2, param=4, epoch=8, last=4)  # the row strides the
 
 
 def _install_pyg_shim():
-    """torch_geometric as far as src/models/grcn.py uses it (harness only, our own code):
-    MessagePassing with aggr 'add' and the source -> target flow, PyG's softmax,
-    remove_self_loops / add_self_loops, and dropout_adj for p = 0."""
+    """torch_geometric as far as src/models/grcn.py and src/models/mmgcn.py use it (harness only,
+    our own code): MessagePassing with aggr 'add' or 'mean' (the sum over a target's in-edges
+    divided by their number, a target without edges zero) and the source -> target flow, PyG's
+    softmax, remove_self_loops / add_self_loops, degree, dropout_adj for p = 0, and
+    nn.inits.uniform(size, t) = t.uniform_(-1 / sqrt(size), 1 / sqrt(size)).  The MMGCN
+    fixtures' initial parameters are what the generator gives after this shim's draws: a
+    BaseModel weight takes in * out uniform draws here before its xavier_normal_."""
     import inspect
+    import math
 
     class MessagePassing(torch.nn.Module):
         def __init__(self, aggr="add", **kw):
             super().__init__()
-            assert aggr == "add", aggr
+            assert aggr in ("add", "mean"), aggr
             self.aggr = aggr
 
         def propagate(self, edge_index, size=None, x=None):
             j, i = edge_index[0], edge_index[1]
-            have = dict(x_j=x[j], x_i=x[i], size_i=x.shape[0], edge_index_i=i)
+            have = dict(x_j=x[j], x_i=x[i], size_i=x.shape[0], edge_index_i=i, edge_index=edge_index, size=size)
             names = [n for n in inspect.signature(self.message).parameters]
             msg = self.message(**{n: have[n] for n in names})
             out = torch.zeros(x.shape[0], msg.shape[1], dtype=msg.dtype).index_add_(0, i, msg)
+            if self.aggr == "mean":
+                out = out / degree(i, x.shape[0], dtype=msg.dtype).clamp_(min=1).unsqueeze(1)
             return self.update(out)
 
         def update(self, aggr_out):
@@ -1104,13 +1111,23 @@ def _install_pyg_shim():
             raise NotImplementedError("dropout_adj: only p = 0 is shimmed")
         return edge_index, None
 
-    tg, nn_, conv, utils = (types.ModuleType(n) for n in ("torch_geometric", "torch_geometric.nn",
-                                                          "torch_geometric.nn.conv", "torch_geometric.utils"))
+    def degree(index, num_nodes=None, dtype=None):
+        n = int(index.max()) + 1 if num_nodes is None else num_nodes
+        return torch.zeros(n, dtype=dtype or torch.float32).index_add_(0, index, torch.ones(index.numel(), dtype=dtype or torch.float32))
+
+    def uniform(size, tensor):
+        if tensor is not None:
+            bound = 1.0 / math.sqrt(size)
+            tensor.data.uniform_(-bound, bound)
+
+    tg, nn_, conv, utils, inits = (types.ModuleType(n) for n in (
+        "torch_geometric", "torch_geometric.nn", "torch_geometric.nn.conv", "torch_geometric.utils",
+        "torch_geometric.nn.inits"))
     conv.MessagePassing = nn_.MessagePassing = MessagePassing
     utils.softmax, utils.remove_self_loops, utils.add_self_loops = softmax, remove_self_loops, add_self_loops
-    utils.dropout_adj = dropout_adj
-    tg.nn, tg.utils, nn_.conv = nn_, utils, conv
-    for m in (tg, nn_, conv, utils):
+    utils.dropout_adj, utils.degree, inits.uniform = dropout_adj, degree, uniform
+    tg.nn, tg.utils, nn_.conv, nn_.inits = nn_, utils, conv, inits
+    for m in (tg, nn_, conv, utils, inits):
         sys.modules[m.__name__] = m
 
 
@@ -1261,10 +1278,197 @@ def capture_grcn(out_dir):
         assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
 
 
+MMGCN_ROWS = dict(rep=16, grad=4, param=4, const=8, epoch=8, last=4)  # row strides of the stored tables
+MMGCN_SEEDS = dict(v=41, t=42)  # feature seeds at which the capture's pre-activation margin holds
+
+
+def _mmgcn_model():
+    from utils.utils import init_seed, get_model
+    from common.trainer import Trainer
+
+    config, train, valid, test = _load("MMGCN", "baby", GRCN_OVERRIDES)
+    hp = _select_hparams(config)
+    init_seed(config["seed"])
+    train.pretrain_setup()
+    model = get_model("MMGCN")(config, train)
+    return config, hp, train, valid, test, model, Trainer(config, model)
+
+
+def capture_mmgcn(out_dir):
+    """MMGCN (reference src/models/mmgcn.py) on the small graph, 48-wide image and 32-wide text
+    features: seed 999, the YAML's sizes, learning_rate and reg_weight 0.001, batches of 512.
+    torch_geometric is the shim above.
+    mmgcn_step0_small.npz: the first two steps: triplets, loss / bpr / reg (reg in float64 on the
+    model's own tensors; it has to account for the rest of the loss), per modality and layer the
+    output x, every gradient and the parameters after Adam, tables of 64 rows or more at the row
+    strides of MMGCN_ROWS; the pre-activation margin (below).
+    mmgcn_small.npz: the initial parameters, the constants (id_embedding, both preferences, the
+    initial `result`), the mean operator as COO, the features, two epochs through the reference's
+    Trainer with the parameters after each, the evaluation of the initial `result` and of the
+    last epoch.
+    The capture fails unless (a) the constants are bit-unchanged after the two epochs and absent
+    from parameters(), and (b) at step 0 every leaky_relu pre-activation of the reference is
+    farther from zero than twice the largest difference, on that tensor, between the reference's
+    float32 pre-activation and the float64 restatement's (tests/mmgcn_ref.py): no float32
+    rounding of either side then moves an element across the kink, so the first step's gradients
+    are comparable.  Threshold and observed minimum are stored."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import mmgcn_ref as R
+
+    shutil.rmtree(os.path.join(DATA_ROOT, "baby"), ignore_errors=True)
+    df = synth.amazon_like(400, 200, 4000, seed=7)
+    synth.write_inter(df, DATA_ROOT, "baby")
+    n_items = int(df.itemID.max()) + 1
+    np.save(os.path.join(DATA_ROOT, "baby", "image_feat_raw.npy"), synth.features(n_items, 48, seed=MMGCN_SEEDS["v"]))
+    np.save(os.path.join(DATA_ROOT, "baby", "text_feat_raw.npy"), synth.features(n_items, 32, seed=MMGCN_SEEDS["t"]))
+    _install_pyg_shim()
+    S = MMGCN_ROWS
+
+    def constants(model):
+        return {"id_embedding": model.id_embedding, "v_gcn.preference": model.v_gcn.preference,
+                "t_gcn.preference": model.t_gcn.preference, "result": model.result}
+
+    # ---- pass 1: the first two steps
+    config, hp, train, valid, test, model, trainer = _mmgcn_model()
+    nu, ni = model.n_users, model.n_items
+    names = tuple(n for n, _ in model.named_parameters())
+    assert names == R.names(), names
+    own = {id(p) for p in model.parameters()}
+    C0 = {k: v.detach().numpy().copy() for k, v in constants(model).items()}
+    for k, v in constants(model).items():
+        assert id(v) not in own and not isinstance(v, torch.nn.Parameter), k
+    init = {n: p.numpy().copy() for n, p in _param_dict(model).items()}
+    feats32 = {"v": model.v_feat, "t": model.t_feat}
+    ei = model.edge_index.numpy()
+    E = ei.shape[1] // 2
+    train_u, train_i = ei[0, :E], ei[1, :E] - nu
+    A64 = R.mean_operator(train_u, train_i, nu, ni)
+    # the reference's pre-activations: what conv_embed_k, linear_layerk and g_layerk return
+    pres = {}
+    for m, g in (("v", model.v_gcn), ("t", model.t_gcn)):
+        for k in (1, 2, 3):
+            for s, mod in (("ph", getattr(g, f"conv_embed_{k}")), ("pu", getattr(g, f"linear_layer{k}")),
+                           ("po", getattr(g, f"g_layer{k}"))):
+                mod.register_forward_hook(lambda _m, _i, o, key=(m, f"{s}{k}"): pres.__setitem__(key, o.detach().clone()))
+    out = {"n_users": np.int64(nu), "n_items": np.int64(ni)}
+    P64 = R.cast({n: torch.from_numpy(v) for n, v in init.items()}, torch.float64)
+    C64 = {k: torch.from_numpy(v).double() for k, v in C0.items() if k != "result"}
+    f64 = {m: f.double() for m, f in feats32.items()}
+    model.train()
+    it = iter(train)
+    for step in range(2):
+        batch = next(it)
+        trainer.optimizer.zero_grad()
+        loss = model.calculate_loss(batch)
+        loss.backward()
+        pre = f"step{step}_"
+        rep = model.result.detach()
+        if step == 0:
+            keep = {}
+            with torch.no_grad():
+                R.forward(P64, C64, f64, A64, keep)
+            margin, worst, fixed_near = np.inf, 0.0, []
+            for (m, key), p32 in pres.items():
+                p64 = keep[m][key]
+                diff = float((p32.double() - p64).abs().max())
+                # The item rows of layer 1's aggregate and the user rows of its Linear read the
+                # preferences alone: functions of seed 999, whatever the feature seeds.  No seed
+                # choice moves them, so an element of theirs inside the margin is listed in the
+                # fixture instead (the reference and the restatement must still agree on its sign).
+                seeded = torch.zeros_like(p32, dtype=torch.bool)
+                if key == "ph1":
+                    seeded[nu:] = True
+                elif key == "pu1":
+                    seeded[:nu] = True
+                inside = p32.abs() <= 2 * diff
+                for r, c in (inside & seeded).nonzero().tolist():
+                    assert float(p32[r, c]) * float(p64[r, c]) > 0, (m, key, r, c)
+                    fixed_near.append(f"{m}.{key}[{r},{c}]: reference {float(p32[r, c]):.4e}, restatement "
+                                      f"{float(p64[r, c]):.4e}, threshold {2 * diff:.4e}")
+                near = float(p32.abs()[~seeded].min())
+                assert near > 2 * diff, f"{m} {key}: a pre-activation at {near:.3e}, reference vs restatement {diff:.3e}: pick other feature seeds"
+                margin, worst = min(margin, near / diff), max(worst, diff)
+                out[f"step0_preact_min.{m}.{key}"] = np.float64(near)
+                out[f"step0_preact_thr.{m}.{key}"] = np.float64(2 * diff)
+            out["step0_preact_seed_fixed_inside"] = np.array(fixed_near)
+            print(f"pre-activations: smallest |pre| / (reference - restatement) = {margin:.1f} (needs > 2), largest "
+                  f"difference {worst:.3e}; inside the margin on rows the feature seeds do not reach: {fixed_near}")
+        u, p, n = batch[0], batch[1] + nu, batch[2] + nu
+        bpr = torch.nn.functional.softplus(-((rep[u] * rep[p]).sum(1) - (rep[u] * rep[n]).sum(1))).mean()
+        ut, it_ = u.repeat_interleave(2), torch.stack([p, n]).t().reshape(-1)
+        E_, pv = model.id_embedding.detach().double(), model.v_gcn.preference.detach().double()
+        reg = float(model.reg_weight) * ((E_[ut] ** 2 + E_[it_] ** 2).mean() + (pv ** 2).mean())
+        assert abs(loss.item() - bpr.item() - reg.item()) <= 3e-7 * abs(loss.item()), (loss.item(), bpr.item(), reg.item())
+        out[pre + "triplets"] = batch.numpy().astype(np.int16)
+        out[pre + "loss"], out[pre + "bpr"], out[pre + "reg"] = (np.float64(v.item()) for v in (loss, bpr, reg))
+        out[pre + "representation"] = rep.numpy()[::S["rep"]].copy()
+        for (m, key), p32 in pres.items():
+            if key.startswith("po"):
+                out[f"{pre}x.{m}.{key[2:]}"] = torch.nn.functional.leaky_relu(p32).numpy()[::S["rep"]].copy()
+        for name, prm in model.named_parameters():
+            out[pre + "grad." + name] = R.rows(prm.grad.numpy(), S["grad"]).copy()
+        trainer.optimizer.step()
+        for name, prm in _param_dict(model).items():
+            out[pre + "param." + name] = R.rows(prm.numpy(), S["param"]).copy()
+    out["row_strides"] = np.array([f"{k}={v}" for k, v in S.items()])
+    out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()] +
+                              [f"{k}={config[k]}" for k in ("embedding_size", "n_layers")])
+    path = os.path.join(out_dir, "mmgcn_step0_small.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}: {os.path.getsize(path) / 1e6:.2f} MB, keys={len(out)}")
+
+    # ---- pass 2: two epochs through the reference's Trainer
+    config, hp, train, valid, test, model, trainer = _mmgcn_model()
+    for n, v in init.items():
+        assert np.array_equal(dict(_param_dict(model))[n].numpy(), v), n
+    for k, v in constants(model).items():
+        assert np.array_equal(v.detach().numpy(), C0[k]), k
+    held = {k: v for k, v in constants(model).items() if k != "result"}
+    out = {"n_users": np.int64(nu), "n_items": np.int64(ni)}
+    out["train_u"], out["train_i"] = train_u.astype(np.int16), train_i.astype(np.int16)
+    idx, val = R.operator_coo(A64)
+    out["mean_adj_idx"], out["mean_adj_val"] = idx.astype(np.int16), val.astype(np.float32)
+    for n, v in init.items():
+        out["init." + n] = R.rows(v, S["param"]).copy()
+    for k, v in C0.items():
+        out["const." + k] = v[::S["const"]].copy()
+    out["v_feat"], out["t_feat"] = model.v_feat.numpy().copy(), model.t_feat.numpy().copy()
+    rec = _Recorder(train)
+    _eval_dump(trainer, model, valid, "init_valid", out)
+    losses = []
+    for epoch in range(2):
+        model.pre_epoch_processing()
+        n0 = len(rec.batches)
+        loss_sum, _ = trainer._train_epoch(train, epoch)
+        trainer.lr_scheduler.step()
+        losses.append(float(loss_sum))
+        out[f"epoch{epoch}_triplets"] = torch.cat(rec.batches[n0:], dim=1).numpy().astype(np.int16)
+        out[f"epoch{epoch}_nbatch"] = np.int64(len(rec.batches) - n0)
+        for name, prm in _param_dict(model).items():
+            out[f"epoch{epoch}_param." + name] = R.rows(prm.numpy(), S["last" if epoch == 1 else "epoch"]).copy()
+    out["epoch_losses"] = np.array(losses)
+    own = {id(p) for p in model.parameters()}
+    for k, v in held.items():  # the constants: the same tensors, the same bits, no parameters
+        assert constants(model)[k] is v and id(v) not in own and np.array_equal(v.detach().numpy(), C0[k]), k
+    _eval_dump(trainer, model, valid, "epoch1_valid", out)
+    _eval_dump(trainer, model, test, "epoch1_test", out)
+    for tag, ld in (("valid", valid), ("test", test)):
+        out[f"{tag}_eval_u"] = ld.get_eval_users().numpy().astype(np.int64)
+        out[f"{tag}_eval_len"] = np.asarray(ld.get_eval_len_list(), dtype=np.int64)
+        out[f"{tag}_eval_items"] = np.concatenate([np.asarray(x, dtype=np.int64) for x in ld.get_eval_items()])
+    out["row_strides"] = np.array([f"{k}={v}" for k, v in S.items()])
+    out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()])
+    path = os.path.join(out_dir, "mmgcn_small.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}: {os.path.getsize(path) / 1e6:.2f} MB, keys={len(out)}")
+    for f in ("mmgcn_small.npz", "mmgcn_step0_small.npz"):
+        assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn")
+    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     _install_shims()
@@ -1283,6 +1487,9 @@ def main():
         return
     if args.only == "grcn":
         capture_grcn(args.out)
+        return
+    if args.only == "mmgcn":
+        capture_mmgcn(args.out)
         return
     if args.only == "mf":
         capture_mf(args.out)
