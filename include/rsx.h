@@ -102,7 +102,8 @@ int rsx_csr_schedule_rebind(const rsx_csr* tmpl, const int64_t* rowptr, int32_t*
  * write-out:
  *
  *   RSX_EPI_STORE     y = alpha*acc
- *   RSX_EPI_LAYERSUM  y = alpha*acc;  s_out = s_in + alpha*acc
+ *   RSX_EPI_LAYERSUM  y = alpha*acc;  s_out = s_in + alpha*acc  (y may be NULL: only the
+ *                     sum is kept; s_in may be NULL = 0)
  *                     (running layer sum of lightgcn.py:124-125 / Horner backward)
  *   RSX_EPI_FINAL     f = ((((s_in + r_add) + aux) + e0) + alpha*acc) * beta (NULL
  *                     terms skipped);  zero0/zero1 rows := 0  (last layer: mean over
@@ -110,17 +111,20 @@ int rsx_csr_schedule_rebind(const rsx_csr* tmpl, const int64_t* rowptr, int32_t*
  *                     from the stored layers E0 = s_in, E1 = r_add, E2 = aux, E3 = e0)
  *   RSX_EPI_ADAM      g = (s_in + alpha*acc) * beta + r_add;  Adam(p, m, v, g)
  *                     (last backward layer fused with torch.optim.Adam,
- *                      src/common/trainer.py:133,238)
- *   RSX_EPI_LAYERGCN  c = cos(acc, e0) (eps 1e-8, F.cosine_similarity);
- *                     y = c*acc;  s_out = s_in + c*acc (s_in may be NULL = 0);
- *                     saves acc (pre-scale) into `aux` and c into `aux_w`
- *                     (src/models/layergcn.py:133-138)
+ *                      src/common/trainer.py:133,238; s_in / r_add may be NULL = 0)
+ *   RSX_EPI_LAYERGCN  z = alpha*acc;  c = cos(z, e0) (eps 1e-8, F.cosine_similarity);
+ *                     y = c*z;  s_out = s_in + c*z (s_in may be NULL = 0);
+ *                     saves z (the rows before the cosine scaling) into `aux` and c
+ *                     into `aux_w`; y, s_out, aux, aux_w may each be NULL
+ *                     (src/models/layergcn.py:133-138; every caller passes alpha = 1)
  *   RSX_EPI_AXPBY     y = alpha*acc + beta*s_in   (general accumulate)
  *   RSX_EPI_LAYERGCN_BWD  backward of the LayerGCN row scaling: with
  *                     dE = alpha*acc + r_add (grad reaching E^k), z = aux (saved
  *                     pre-scale rows), c = aux_w, e = e0, nz/ne eps-clamped norms:
  *                       y     = c*dE + <dE,z> (e/(nz ne) - c z/nz^2)      (dZ^k)
  *                       s_out = s_in + <dE,z> (z/(nz ne) - c e/ne^2)     (d ego)
+ *                     (a norm below the eps is a constant: its c z/nz^2 or c e/ne^2 term
+ *                      is dropped; r_add, s_in, y, s_out may each be NULL)
  *   RSX_EPI_ADD     y = (alpha*acc + s_in + r_add) * beta  (s_in / r_add may be NULL;
  *                     y may alias s_in) — row-block sums of the sharded path
  *   Every kind also zeroes the zero0 / zero1 rows when those are non-NULL.
@@ -130,9 +134,14 @@ int rsx_csr_schedule_rebind(const rsx_csr* tmpl, const int64_t* rowptr, int32_t*
  * floats of partial sums followed by n_long int32 arrival counters, which must
  * be zero before the first call (allocate zero-filled; every call leaves them
  * zero again).  NULL is allowed when n_long == 0.  One launch does the whole
- * product: the long rows' chunk partials first, then one block per long row sums
- * them in chunk order, so results are deterministic.  A slab (with its
- * counters) must not be shared by two calls in flight at once.
+ * product (two when more than 1,024 rows are split: the fixups then follow in a
+ * launch of their own): the long rows' chunk partials first, then one block per
+ * long row sums them in a fixed order -- chunk order for a row of up to
+ * 256 / (d / 4) chunks; beyond that each of the block's 256 / (d / 4) lane groups
+ * sums every (256 / (d / 4))-th partial in four interleaved accumulators and the
+ * group sums are added in group order -- so results are deterministic and do not
+ * depend on which chunk finished last.  A slab (with its counters) must not be
+ * shared by two calls in flight at once.
  * d must be one of 32, 64, 128, 256.
  */
 enum {
@@ -168,7 +177,9 @@ typedef struct rsx_epilogue {
     float* p;
     float* m;
     float* v;
-    float* g_out;      /* ADAM: optional copy of the gradient row (autograd path) */
+    float* g_out;      /* ADAM: optional copy of the gradient row as the moments saw it:
+                        * g + weight_decay * p_old (g itself when weight_decay = 0);
+                        * written under halt too */
     const float* e0;   /* LAYERGCN(_BWD): ego rows */
     float* aux;        /* LAYERGCN: pre-scale rows written; LAYERGCN_BWD: read */
     float* aux_w;      /* LAYERGCN: cosine weight per row written; LAYERGCN_BWD: read */
@@ -181,7 +192,12 @@ typedef struct rsx_epilogue {
      *   RSX_TAG_SPARSE_X  X rows not tagged are zero: their gathers are skipped;
      *   RSX_TAG_SPARSE_S  s_in rows not tagged are zero (not loaded);
      *   RSX_TAG_SPARSE_R  r_add rows not tagged are zero (not loaded);
-     *   RSX_TAG_ZERO      zero0 / zero1 are cleared on tagged rows only. */
+     *   RSX_TAG_ZERO      zero0 / zero1 are cleared on tagged rows only.
+     * SPARSE_S is honoured by LAYERSUM, FINAL, ADAM, AXPBY and ADD, SPARSE_R by FINAL,
+     * ADAM (r_add or reg_cnt) and ADD (r_add only: ADD reads and clears the counts of
+     * every row it writes).  The LayerGCN kinds load s_in and r_add on every row whatever
+     * the flags say.  ROWS, SPARSE_X and ZERO hold for every kind; under ROWS an
+     * untagged row's zero0 / zero1 / reg_cnt are left alone as well. */
     const int32_t* row_tag;
     int32_t tag;
     int32_t tag_flags;
@@ -189,8 +205,9 @@ typedef struct rsx_epilogue {
      * r = (cnt[3r] k[0] + cnt[3r+1] k[1] + cnt[3r+2] k[2]) * p_old (what the fused
      * LightGCN BPR leaves instead of a dense R; p_old = the row of `p`).  Used
      * instead of r_add when non-NULL.  ADAM: with RSX_TAG_ZERO the counts of the
-     * tagged rows are cleared too.  ADD: s = ((acc + s_in) + r) * beta, and every
-     * row's counts are cleared (rows here are relative to reg_cnt and p). */
+     * tagged rows are cleared too (without it they are left as they are).  ADD:
+     * s = ((alpha*acc + s_in) + r) * beta, and every row's counts are cleared (rows
+     * here are relative to reg_cnt and p). */
     int32_t* reg_cnt;
     const float* reg_k;
     /* optional: the tag is read from device memory (graph-captured steps) */
