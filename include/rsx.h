@@ -1735,6 +1735,97 @@ int rsx_mmgcn_loss_fwd(const rsx_mmgcn_loss_args* a, float* out, float* result, 
 int rsx_mmgcn_loss_bwd(const rsx_mmgcn_loss_args* a, const float* go, float* g, void* ws, size_t ws_bytes,
                        rsx_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* GRCN: edge attention, the refined edge weight, SDDMM, loss (grcn.hip)      */
+/* ------------------------------------------------------------------------ */
+/*
+ * The graph of these calls is a CSR by TARGET row over n nodes: rowptr int64 [n + 1], col int32
+ * [nnz] the SOURCE of slot e, and rev int32 [nnz] the slot of the reversed edge (rev[rev[e]] = e,
+ * col[rev[e]] = row(e)): the structure is symmetric (rsx.grcn.target_csr).  n, nnz < 2^31.  A col
+ * or rev entry outside its range is skipped (its alpha, weight and gradients are 0), never read
+ * through.  Widths d in {64, 128}, else RSX_ERR_UNSUPPORTED; tables 16-byte aligned.  Every
+ * kernel is deterministic (no float atomics, fixed orders), works on the caller's buffers and is
+ * stream-ordered: no allocation, no synchronisation, graph-capturable.
+ *
+ * rsx_grcn_hub_degree(): rows with more in-edges than this are walked by a whole block (lane
+ * groups take strided edges, their states are merged in lane-group order), rows at or below it
+ * by one lane group.
+ *
+ * rsx_grcn_attn_fwd (grcn.py:46-76): for every row t, s_e = <x_t, x_col[e]> over its in-edges,
+ * alpha[e] = exp(s_e - max) / sum exp(s - max) in slot order and rep_t = x_t + sum alpha_e
+ * x_col[e]; a row without in-edges gets rep = x.  x is general (the row max is subtracted).
+ * PyG's + 1e-16 in the denominator is dropped: the sum contains exp(0) = 1, so 1e-16 is far below
+ * its float32 rounding.
+ */
+int32_t rsx_grcn_hub_degree(void);
+int rsx_grcn_attn_fwd(const float* x, const int64_t* rowptr, const int32_t* col, int64_t n, int64_t nnz, int32_t d,
+                      float* alpha, float* rep, rsx_stream_t stream);
+/*
+ * Its backward, two launches.  Given g = d rep [n, d] and dalpha_ext [nnz] (NULL = 0), with
+ * da_e = <g_t, x_s> + dalpha_ext[e] and ds_e = alpha_e (da_e - sum over row t of alpha da):
+ *   dx_t = g_t + sum over row t of ds_e x_s        (row-local; also writes ds [nnz])
+ *   dx_s += ds_e x_t + alpha_e g_t                 (row s gathers its out-edges through rev)
+ * dx [n, d] is written whole; ds is scratch the caller owns.
+ */
+int rsx_grcn_attn_bwd(const float* g_rep, const float* dalpha_ext, const float* x, const float* alpha,
+                      const int64_t* rowptr, const int32_t* col, const int32_t* rev, int64_t n, int64_t nnz, int32_t d,
+                      float* ds, float* dx, rsx_stream_t stream);
+/*
+ * The refined edge weight (grcn.py:272-281): w_e = relu(max over the n_mod in {1, 2} modalities
+ * of alpha_m[e] conf[col[e], m]), conf [n, n_mod]; val[e] = w_e and valT[rev[e]] = w_e (A_w and
+ * its transpose share rowptr and col).  Modality 1 wins only when strictly larger.
+ */
+int rsx_grcn_refine_fwd(int32_t n_mod, const float* alpha0, const float* alpha1, const float* conf,
+                        const int32_t* col, const int32_t* rev, int64_t n, int64_t nnz, float* val, float* valT,
+                        rsx_stream_t stream);
+/*
+ * The SDDMM of the id GCN's backward (x + h1 + h2, h1 = A_w x, h2 = A_w h1; G = d id_rep,
+ * D = G + A_w^T G): dw[e] = <G_t, h1_s> + <D_t, x_s>, t = row(e) = col[rev[e]], s = col[e].
+ */
+int rsx_grcn_edge_dots(const float* G, const float* h1, const float* D, const float* x, const int32_t* col,
+                       const int32_t* rev, int64_t n, int64_t nnz, int32_t d, float* dw, rsx_stream_t stream);
+/*
+ * The refine's backward from dw [nnz]: the winning modality a of an edge is recomputed with
+ * the forward's arithmetic; on edges with w_e > 0, dconf[s, a] sums dw_e alpha_a[e] over the
+ * edges whose source is s (a wave a source row, through rev: one writer an element; dconf
+ * [n, n_mod] is written whole) and dalpha_a[e] = dw_e conf[s, a]; every other dalpha_m[e] is 0.
+ */
+int rsx_grcn_refine_bwd(int32_t n_mod, const float* alpha0, const float* alpha1, const float* conf, const float* dw,
+                        const int64_t* rowptr, const int32_t* rev, int64_t n, int64_t nnz, float* dalpha0,
+                        float* dalpha1, float* dconf, rsx_stream_t stream);
+/* out = g .* slope(y) over n_elems floats (a multiple of 4), y a saved leaky_relu output: slope
+ * 1 where y > 0, else 0.01 (the content MLP's backward, grcn.py:141). */
+int rsx_grcn_leaky_bwd(const float* g, const float* y, int64_t n_elems, float* out, rsx_stream_t stream);
+/*
+ * GRCN's loss (grcn.py:300-333) on the representation [id_rep | rep_v | rep_t] given as its
+ * tables, not concatenated: id_rep [n, dx], rep_v and rep_t [n, dc] (rep_t and pref_t NULL
+ * together: image alone), n = n_users + n_items, dx + n_mod dc <= 256.  With x_b the BPR score
+ * difference on the whole representation:
+ *   out = {bpr + reg, bpr, reg},  bpr = mean softplus(-x_b),
+ *   reg = reg_weight (sum_b (2 |E_u|^2 + |E_p|^2 + |E_n|^2) / (2 batch dx) + mean(pref_v^2)
+ *                     + sum over the modalities of sum_b |pref_m[u]|^2 / (batch dc))
+ * With `result` non-NULL the forward also writes result[row, 0 : width] = the tables side by
+ * side at leading dimension ld >= width (a multiple of 4; the columns past the width are left).
+ * The backward writes EVERY row of g_id [n, dx], g_v, g_t [n, dc] (zero off the batch, repeated
+ * rows summed by the first-occurrence walk) and of the regulariser's gradients gE [n, dx], gpv,
+ * gpt [n_users, dc] (gpv includes the whole-table term).  go: the upstream gradient, a device
+ * word.  batch <= 65536, n < 2^31; ws >= rsx_grcn_loss_ws_bytes(batch, width) (0: unsupported).
+ */
+typedef struct rsx_grcn_loss_args {
+    const float *id_rep, *rep_v, *rep_t;
+    const float *E, *pref_v, *pref_t;
+    const int64_t* triplets; /* [3, batch] users, positives, negatives (item ids, not offset) */
+    int64_t n_users, n_items, batch;
+    int32_t dx, dc;
+    float reg_weight;
+    int32_t pad0;
+} rsx_grcn_loss_args;
+size_t rsx_grcn_loss_ws_bytes(int64_t batch, int32_t width);
+int rsx_grcn_loss_fwd(const rsx_grcn_loss_args* a, float* out, float* result, int64_t ld, void* ws, size_t ws_bytes,
+                      rsx_stream_t stream);
+int rsx_grcn_loss_bwd(const rsx_grcn_loss_args* a, const float* go, float* g_id, float* g_v, float* g_t, float* gE,
+                      float* gpv, float* gpt, void* ws, size_t ws_bytes, rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

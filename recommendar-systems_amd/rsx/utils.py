@@ -12,7 +12,8 @@ MODELS = {"lightgcn": ("rsx.lightgcn", "LightGCN"), "layergcn": ("rsx.layergcn",
           "smore": ("rsx.smore", "SMORE"), "bpr": ("rsx.bpr", "BPR"), "vbpr": ("rsx.vbpr", "VBPR"),
           "bm3": ("rsx.bm3", "BM3"), "mgcn": ("rsx.mgcn", "MGCN"),
           "freedom": ("rsx.freedom", "FREEDOM"), "lattice": ("rsx.lattice", "LATTICE"),
-          "lgmrec": ("rsx.lgmrec", "LGMRec"), "mmgcn": ("rsx.mmgcn", "MMGCN")}
+          "lgmrec": ("rsx.lgmrec", "LGMRec"), "mmgcn": ("rsx.mmgcn", "MMGCN"),
+          "grcn": ("rsx.grcn", "GRCN")}
 
 
 def get_local_time():
