@@ -1475,9 +1475,9 @@ int rsx_freedom_loss_bwd(const rsx_freedom_args* a, const float* go, float* gE, 
  * rsx_lattice_loss_bwd, given the upstream gradient go (device f32 [1]), writes EVERY row of
  * gE [n_users + n_items, d] and gH [n_items, d]: zero off the batch's rows; an item row of gH is
  * the row's gE sent through the normalise Jacobian (g - hn <hn, g>) / max(|h|, 1e-12).  Rows
- * repeated in the batch are summed in an order fixed by the triplets alone (freedom.hip's
- * first-occurrence walk): no float atomics, bit-identical from run to run.  The backward
- * recomputes the scores: it needs nothing the forward left in ws.
+ * repeated in the batch are summed in an order fixed by the triplets alone (the
+ * first-occurrence walk, csrc/rsx_triplet.hpp): no float atomics, bit-identical from run to
+ * run.  The backward recomputes the scores: it needs nothing the forward left in ws.
  * A triplet with an index outside its table makes the loss NaN and contributes no gradient.
  * ws >= rsx_lattice_ws_bytes(batch, d) bytes (0 for an unsupported shape).  d in {64, 128},
  * 1 <= batch <= 65536, tables below 2^31 rows, else RSX_ERR_UNSUPPORTED; a NULL E / H /

@@ -6,20 +6,11 @@
 //                                   projected feature tables, weighted by reg_weight
 // and their autograd backward (the gathers' index_put scatter-adds).
 //
-// Layout: a d-wide row is one lane group of L = d / 4 float4 lanes, so a wave64 carries
-// G = 64 / L rows (4 at d = 64, 2 at d = 128): rsx_triplet.hpp's RowGeom.
-//
-// Forward launches:  loss_rows (one lane group a triplet: the three scores, the stable
-//   softplus, block partials in row order), finish (the partials in index order).  No atomics.
-// Backward launches: memset of gE / gT / gV (every row is written: zero off the batch),
-//   grad_rows (the scores again, the three coefficients of a triplet, its user-row
-//   contribution stored ONCE in the workspace, and the batch's keys as int32), sum_rows.
-//   sum_rows is the per-destination sum through the inverted index, the index being the
-//   key lists themselves: rsx_triplet.hpp's first-occurrence walk (one wave per occurrence,
-//   3 B waves; at B = 2048 it is 4096 waves of at most 16 chunk loads).  A user row
-//   adds the stored contribution rows; an item row adds coefficient * E[user] for the id,
-//   text and image coefficient of each occurrence (positives +, negatives -) in one walk, as
-//   all three tables share the item's occurrence list.
+// The protocol (lane-group layout, block partials, keys, the first-occurrence walk, workspace,
+// argument checks) is rsx_triplet.hpp's; this file has the three-score triplet and what the
+// walk adds: a user row adds the stored contribution rows; an item row adds coefficient *
+// E[user] for the id, text and image coefficient of each occurrence in one walk, as all three
+// tables share the item's occurrence list.
 #include "rsx_triplet.hpp"
 
 namespace rsx {
@@ -133,40 +124,28 @@ __global__ __launch_bounds__(256) void grad_rows(Args a, const float* __restrict
     }
 }
 
-// The per-destination sums (rsx_triplet.hpp's walk).  Wave w < B: user occurrence w; else
-// item occurrence w - B of [positives; negatives].
+// The per-destination sums (rsx_triplet.hpp's walk)
 template <int D>
 __global__ __launch_bounds__(256) void sum_rows(Args a, const float* __restrict__ occU, const float* __restrict__ coef,
                                                 const int32_t* __restrict__ ku, const int32_t* __restrict__ ki,
                                                 float* __restrict__ gE, float* __restrict__ gT,
                                                 float* __restrict__ gV) {
-    constexpr int L = RowGeom<D>::L;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), B = a.B;
-    if (w >= 3 * B) return;  // wave-uniform, as every branch on w, j and key below
-    const bool user = w < B;
-    const int32_t* __restrict__ keys = user ? ku : ki;
-    const int64_t n = user ? B : 2 * B, j = user ? w : w - B;
-    const int32_t key = keys[j];
-    if (key < 0 || !leads(keys, j, key, lane)) return;
-    const int g = lane / L, c = (lane % L) * 4;
+    Walk<D> w;
+    if (!w.begin(ku, ki, a.B)) return;
+    const int c = w.c;
+    const int32_t key = w.key;
     float4 acc[3] = {f4(0.f), f4(0.f), f4(0.f)};
-    for_each_match<D>(keys, j, n, key, lane, [&](int64_t mine) {
-        if (user) {
-            acc[0] = add4(acc[0], ld4(occU + mine * D + c));
-        } else {
-            const int64_t b = mine < B ? mine : mine - B;
-            const float sgn = mine < B ? 1.f : -1.f;
-            const float4 u = ld4(a.E + (int64_t)ku[b] * D + c);
-            acc[0] = fma4(sgn * coef[b], u, acc[0]);
-            if (gT) acc[1] = fma4(sgn * coef[B + b], u, acc[1]);
-            if (gV) acc[2] = fma4(sgn * coef[2 * B + b], u, acc[2]);
-        }
-    });
+    w.each([&](int64_t occ) { acc[0] = add4(acc[0], ld4(occU + occ * D + c)); },
+           [&](int64_t b, float sgn) {
+               const float4 u = ld4(a.E + (int64_t)ku[b] * D + c);
+               acc[0] = fma4(sgn * coef[b], u, acc[0]);
+               if (gT) acc[1] = fma4(sgn * coef[a.B + b], u, acc[1]);
+               if (gV) acc[2] = fma4(sgn * coef[2 * a.B + b], u, acc[2]);
+           });
 #pragma unroll
-    for (int k = 0; k < 3; ++k) tree_rows<L>(acc[k]);
-    if (g != 0) return;
-    if (user) {
+    for (int k = 0; k < 3; ++k) tree_rows<Walk<D>::L>(acc[k]);
+    if (w.g != 0) return;
+    if (w.user) {
         st4(gE + (int64_t)key * D + c, acc[0]);
     } else {
         st4(gE + (a.nu + key) * D + c, acc[0]);
@@ -191,9 +170,8 @@ inline int check(const rsx_freedom_args* a, void* ws, size_t ws_bytes, Args& k) 
 
 template <int D>
 int fwd(const Args& k, float* out, void* ws, hipStream_t s) {
-    constexpr int RPB = RowGeom<D>::RPB;
     const TripletWs w = carve(ws, k.B, D);
-    const int nblk = (int)((k.B + RPB - 1) / RPB);
+    const int nblk = rows_blocks<D>(k.B);
     hipLaunchKernelGGL(loss_rows<D>, dim3(nblk), dim3(256), 0, s, k, w.part);
     hipLaunchKernelGGL(finish, dim3(1), dim3(64), 0, s, (const float*)w.part, nblk, k.B, k.reg, out);
     return last_rc();
@@ -201,16 +179,13 @@ int fwd(const Args& k, float* out, void* ws, hipStream_t s) {
 
 template <int D>
 int bwd(const Args& k, const float* go, float* gE, float* gT, float* gV, void* ws, hipStream_t s) {
-    constexpr int RPB = RowGeom<D>::RPB;
     const TripletWs w = carve(ws, k.B, D);
-    hipError_t e;
-    if ((e = hipMemsetAsync(gE, 0, (size_t)(k.nu + k.ni) * D * sizeof(float), s)) != hipSuccess) return hip_rc(e);
-    if (gT && (e = hipMemsetAsync(gT, 0, (size_t)k.ni * D * sizeof(float), s)) != hipSuccess) return hip_rc(e);
-    if (gV && (e = hipMemsetAsync(gV, 0, (size_t)k.ni * D * sizeof(float), s)) != hipSuccess) return hip_rc(e);
-    const int nblk = (int)((k.B + RPB - 1) / RPB);
-    hipLaunchKernelGGL(grad_rows<D>, dim3(nblk), dim3(256), 0, s, k, go, w.occU, w.coef, w.ku, w.ki);
-    hipLaunchKernelGGL(sum_rows<D>, dim3((unsigned)((3 * k.B + 3) / 4)), dim3(256), 0, s, k, (const float*)w.occU,
-                       (const float*)w.coef, (const int32_t*)w.ku, (const int32_t*)w.ki, gE, gT, gV);
+    const size_t items = (size_t)k.ni * D;
+    // every row is written: zero off the batch
+    const int rc = zero_tables({{gE, (size_t)(k.nu + k.ni) * D}, {gT, items}, {gV, items}}, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(grad_rows<D>, dim3(rows_blocks<D>(k.B)), dim3(256), 0, s, k, go, w.occU, w.coef, w.ku, w.ki);
+    launch_walk(sum_rows<D>, k.B, s, k, w.occU, w.coef, w.ku, w.ki, gE, gT, gV);
     return last_rc();
 }
 

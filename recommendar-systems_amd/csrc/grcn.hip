@@ -18,8 +18,9 @@
 //  * attn_bwd: the row-local part (da, the row's sum, ds, dx_t) and the gather through rev
 //    (dx_s += ds_e x_t + alpha_e g_t), two launches.
 //  * the loss on the three representation tables side by side (a wave a triplet: lane l the
-//    columns 4 l .. 4 l + 3 of [id_rep | rep_v | rep_t], at most 256 wide), `result`, and the
-//    backward with rsx_triplet.hpp's first-occurrence walk.
+//    columns 4 l .. 4 l + 3 of [id_rep | rep_v | rep_t], at most 256 wide) and `result`:
+//    rsx_triplet.hpp's protocol at width 256 (one-score triplet, block partials, keys, walk,
+//    workspace); its own: the concatenated row, the regularisers and their count gradients.
 //
 // Row kernels: a row is a lane group of d / 4 float4 lanes.  A row of more than kHubDegree
 // in-edges is walked by its whole block instead: lane group g takes the edges g, g + RPB, ...
@@ -375,9 +376,8 @@ struct LossArgs {
     float reg_weight;
 };
 
-// lane l's float4 of a row of the concatenated representation (zero past its width)
-__device__ __forceinline__ float4 rep4(const LossArgs& a, int64_t row, int lane) {
-    int col = 4 * lane;
+// the float4 at column col of a row of the concatenated representation (zero past its width)
+__device__ __forceinline__ float4 rep4(const LossArgs& a, int64_t row, int col) {
     if (col < a.dx) return ld4(a.id + row * a.dx + col);
     col -= a.dx;
     if (col < a.dc) return ld4(a.rv + row * a.dc + col);
@@ -386,33 +386,20 @@ __device__ __forceinline__ float4 rep4(const LossArgs& a, int64_t row, int lane)
     return f4(0.f);
 }
 
-struct Trip : TripIdx {
-    float4 ur, pr, nr;
-    float x;  // <u, p> - <u, n>
-};
-
-__device__ __forceinline__ void load_trip(const LossArgs& a, int64_t b, int lane, Trip& t) {
-    load_idx(a.trip, a.B, b, a.nu, a.ni, t);
-    t.ur = t.pr = t.nr = f4(0.f);
-    if (!t.ok) {  // wave-uniform
-        t.x = __builtin_nanf("");
-        return;
-    }
-    t.ur = rep4(a, t.u, lane);
-    t.pr = rep4(a, a.nu + t.p, lane);
-    t.nr = rep4(a, a.nu + t.n, lane);
-    t.x = group_sum<kWave>(dot4(t.ur, t.pr)) - group_sum<kWave>(dot4(t.ur, t.nr));
+__device__ __forceinline__ void load_trip(const LossArgs& a, int64_t b, int c, ScoreTrip& t) {
+    load_score_trip<256>(
+        a.trip, a.B, b, a.nu, a.ni, c, [&](int64_t u, int c) { return rep4(a, u, c); },
+        [&](int64_t i, int c) { return rep4(a, a.nu + i, c); }, t);
 }
 
 // part[block] = sums over the block's four triplets of {softplus(-x), 2 |E_u|^2 + |E_p|^2 + |E_n|^2,
 // |pref_v[u]|^2, |pref_t[u]|^2}
 __global__ __launch_bounds__(256) void loss_rows(LossArgs a, float* __restrict__ part) {
     const RowGeom<256> r;  // a wave a triplet
-    const int lane = threadIdx.x & (kWave - 1);
     float v[kTerms] = {0.f, 0.f, 0.f, 0.f};
     if (r.b < a.B) {  // wave-uniform
-        Trip t;
-        load_trip(a, r.b, lane, t);
+        ScoreTrip t;
+        load_trip(a, r.b, r.c, t);
         v[0] = softplus_neg(t.x);
         if (t.ok) {
             float e = 0.f, p0 = 0.f, p1 = 0.f;
@@ -475,7 +462,7 @@ __global__ __launch_bounds__(256) void write_result(LossArgs a, int64_t ld, floa
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t n = a.nu + a.ni;
     for (int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += (int64_t)gridDim.x * 4)
-        if (4 * lane < a.W) st4(out + row * ld + 4 * lane, rep4(a, row, lane));
+        if (4 * lane < a.W) st4(out + row * ld + 4 * lane, rep4(a, row, 4 * lane));
 }
 
 // Per triplet b: coef[b] = d total / d x_b (upstream included), occU[b] = coef (rep_p - rep_n)
@@ -485,17 +472,16 @@ __global__ __launch_bounds__(256) void loss_grad_rows(LossArgs a, const float* _
                                                       float* __restrict__ coef, int32_t* __restrict__ ku,
                                                       int32_t* __restrict__ ki) {
     const RowGeom<256> r;
-    const int lane = threadIdx.x & (kWave - 1);
     const int64_t b = r.b;
     if (b >= a.B) return;  // wave-uniform
-    Trip t;
-    load_trip(a, b, lane, t);
-    const float ck = t.ok ? -*go / (float)a.B * sigmoid_neg(t.x) : 0.f;
+    ScoreTrip t;
+    load_trip(a, b, r.c, t);
+    const float ck = bpr_coef(t, go, a.B);
     if (r.c < a.W) {
         st4(occU + b * a.W + r.c, mul4(ck, sub4(t.pr, t.nr)));
         st4(occR + b * a.W + r.c, t.ur);
     }
-    if (lane == 0) {
+    if (r.c == 0) {
         coef[b] = ck;
         store_keys(t, a.B, b, ku, ki);
     }
@@ -513,35 +499,30 @@ __global__ __launch_bounds__(256) void pref_whole_grad(LossArgs a, const float* 
         st4(gpv + 4 * i, mul4(k, ld4(a.pv + 4 * i)));
 }
 
-// The per-destination sums (rsx_triplet.hpp's walk, one lane group a wave).  Wave w < B: user
-// occurrence w; else item occurrence w - B of [positives; negatives].  The leader of a row also
-// counts the row's occurrences: the regularisers' gradients are count times the row.
+// The per-destination sums (rsx_triplet.hpp's walk, one lane group a wave).  The leader of a row
+// also counts the row's occurrences: the regularisers' gradients are count times the row.
 __global__ __launch_bounds__(256) void loss_sum_rows(LossArgs a, const float* __restrict__ go,
                                                      const float* __restrict__ occU, const float* __restrict__ occR,
                                                      const float* __restrict__ coef, const int32_t* __restrict__ ku,
                                                      const int32_t* __restrict__ ki, LossGrads G) {
-    const int lane = threadIdx.x & (kWave - 1), c = 4 * lane;
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), B = a.B;
-    if (w >= 3 * B) return;  // wave-uniform, as every branch on w, j and key below
-    const bool user = w < B;
-    const int32_t* __restrict__ keys = user ? ku : ki;
-    const int64_t n = user ? B : 2 * B, j = user ? w : w - B;
-    const int32_t key = keys[j];
-    if (key < 0 || !leads(keys, j, key, lane)) return;
+    Walk<256> w;
+    if (!w.begin(ku, ki, a.B)) return;
+    const int c = w.c;
+    const int64_t B = a.B;
+    const bool user = w.user;
     float4 acc = f4(0.f);
     float cnt = 0.f;
     const bool mine_cols = c < a.W;
-    for_each_match<256>(keys, j, n, key, lane, [&](int64_t mine) {
-        cnt += 1.f;
-        if (!mine_cols) return;
-        if (user) {
-            acc = add4(acc, ld4(occU + mine * a.W + c));
-        } else {
-            const int64_t b = mine < B ? mine : mine - B;
-            acc = fma4(mine < B ? coef[b] : -coef[b], ld4(occR + b * a.W + c), acc);
-        }
-    });
-    const int64_t row = user ? (int64_t)key : a.nu + key;
+    w.each(
+        [&](int64_t occ) {
+            cnt += 1.f;
+            if (mine_cols) acc = add4(acc, ld4(occU + occ * a.W + c));
+        },
+        [&](int64_t b, float sgn) {
+            cnt += 1.f;
+            if (mine_cols) acc = fma4(sgn * coef[b], ld4(occR + b * a.W + c), acc);
+        });
+    const int64_t row = user ? (int64_t)w.key : a.nu + w.key;
     int col = c;
     if (col < a.dx) {
         st4(G.g_id + row * a.dx + col, acc);
@@ -563,27 +544,21 @@ __global__ __launch_bounds__(256) void loss_sum_rows(LossArgs a, const float* __
     }
 }
 
+// the shared workspace for a wave a triplet and W-wide rows (occR is its extra row buffer, occX),
+// then partw [kSqBlocks]
 struct LossWs {
-    float *part, *partw, *occU, *occR, *coef;
-    int32_t *ku, *ki;
-    size_t total;
+    TripletWs t;
+    float* partw;
 };
 inline LossWs carve(void* ws, int64_t B, int W) {
-    LossWs w;
-    Carver cv(ws);
-    w.part = cv.take<float>((size_t)((B + 3) / 4) * kTerms * sizeof(float));
-    w.partw = cv.take<float>((size_t)kSqBlocks * sizeof(float));
-    w.occU = cv.take<float>((size_t)B * W * sizeof(float));
-    w.occR = cv.take<float>((size_t)B * W * sizeof(float));
-    w.coef = cv.take<float>((size_t)B * sizeof(float));
-    w.ku = cv.take<int32_t>((size_t)B * sizeof(int32_t));  // (256-byte pieces: match256's padding)
-    w.ki = cv.take<int32_t>((size_t)2 * B * sizeof(int32_t));
-    w.total = cv.total();
+    LossWs w{carve_triplet(ws, B, 256, kTerms, 1, 1, W), nullptr};
+    w.partw = w.t.cv.take<float>((size_t)kSqBlocks * sizeof(float));
     return w;
 }
 
 inline bool width_ok(int d) { return d == 64 || d == 128; }
 
+// (not check_triplet: two widths and their sum are judged before the pointers)
 inline int loss_check(const rsx_grcn_loss_args* a, void* ws, size_t ws_bytes, LossArgs& k) {
     if (!a || a->batch < 1 || a->n_users < 1 || a->n_items < 1) return RSX_ERR_ARG;
     if (!width_ok(a->dx) || !width_ok(a->dc)) return RSX_ERR_UNSUPPORTED;
@@ -715,7 +690,7 @@ int rsx_grcn_leaky_bwd(const float* g, const float* y, int64_t n_elems, float* o
 
 size_t rsx_grcn_loss_ws_bytes(int64_t batch, int32_t width) {
     if (batch < 1 || batch > kMaxBatch || width < 128 || width > 256 || width % 64) return 0;
-    return grcn::carve(nullptr, batch, width).total;
+    return grcn::carve(nullptr, batch, width).t.cv.total();
 }
 
 int rsx_grcn_loss_fwd(const rsx_grcn_loss_args* a, float* out, float* result, int64_t ld, void* ws, size_t ws_bytes,
@@ -726,10 +701,10 @@ int rsx_grcn_loss_fwd(const rsx_grcn_loss_args* a, float* out, float* result, in
     if (!out || !aligned16(result) || (result && (ld < k.W || ld % 4))) return RSX_ERR_ARG;
     hipStream_t s = as_stream(stream);
     const grcn::LossWs w = grcn::carve(ws, k.B, k.W);
-    const int nblk = (int)((k.B + 3) / 4);
-    hipLaunchKernelGGL(grcn::loss_rows, dim3(nblk), dim3(256), 0, s, k, w.part);
+    const int nblk = rows_blocks<256>(k.B);
+    hipLaunchKernelGGL(grcn::loss_rows, dim3(nblk), dim3(256), 0, s, k, w.t.part);
     hipLaunchKernelGGL(grcn::sq_partials, dim3(grcn::kSqBlocks), dim3(256), 0, s, k.pv, k.nu * k.dc / 4, w.partw);
-    hipLaunchKernelGGL(grcn::loss_finish, dim3(1), dim3(64), 0, s, k, (const float*)w.part, nblk,
+    hipLaunchKernelGGL(grcn::loss_finish, dim3(1), dim3(64), 0, s, k, (const float*)w.t.part, nblk,
                        (const float*)w.partw, out);
     if (result)
         hipLaunchKernelGGL(grcn::write_result, dim3(grcn::capped((k.nu + k.ni + 3) / 4, 4096)), dim3(256), 0, s, k, ld,
@@ -747,24 +722,18 @@ int rsx_grcn_loss_bwd(const rsx_grcn_loss_args* a, const float* go, float* g_id,
                           (const void*)gpt})
         if (!aligned16(p)) return RSX_ERR_ARG;
     hipStream_t s = as_stream(stream);
-    const grcn::LossWs w = grcn::carve(ws, k.B, k.W);
+    const TripletWs w = grcn::carve(ws, k.B, k.W).t;
     const size_t n = (size_t)(k.nu + k.ni);
-    hipError_t e;
-    if ((e = hipMemsetAsync(g_id, 0, n * k.dx * sizeof(float), s)) != hipSuccess) return hip_rc(e);
-    if ((e = hipMemsetAsync(gE, 0, n * k.dx * sizeof(float), s)) != hipSuccess) return hip_rc(e);
-    if ((e = hipMemsetAsync(g_v, 0, n * k.dc * sizeof(float), s)) != hipSuccess) return hip_rc(e);
-    if (k.rt) {
-        if ((e = hipMemsetAsync(g_t, 0, n * k.dc * sizeof(float), s)) != hipSuccess) return hip_rc(e);
-        if ((e = hipMemsetAsync(gpt, 0, (size_t)k.nu * k.dc * sizeof(float), s)) != hipSuccess) return hip_rc(e);
-    }
+    // (gpv: pref_whole_grad writes every row); the text tables only when the modality is present
+    const int zrc = zero_tables({{g_id, n * k.dx}, {gE, n * k.dx}, {g_v, n * k.dc}, {k.rt ? g_t : nullptr, n * k.dc},
+                                 {k.rt ? gpt : nullptr, (size_t)k.nu * k.dc}}, s);
+    if (zrc) return zrc;
     hipLaunchKernelGGL(grcn::pref_whole_grad, dim3(grcn::capped((k.nu * k.dc / 4 + 255) / 256, 4096)), dim3(256), 0, s,
                        k, go, gpv);
-    hipLaunchKernelGGL(grcn::loss_grad_rows, dim3((unsigned)((k.B + 3) / 4)), dim3(256), 0, s, k, go, w.occU, w.occR,
+    hipLaunchKernelGGL(grcn::loss_grad_rows, dim3(rows_blocks<256>(k.B)), dim3(256), 0, s, k, go, w.occU, w.occX,
                        w.coef, w.ku, w.ki);
     const grcn::LossGrads G{g_id, g_v, g_t, gE, gpv, gpt};
-    hipLaunchKernelGGL(grcn::loss_sum_rows, dim3((unsigned)((3 * k.B + 3) / 4)), dim3(256), 0, s, k, go,
-                       (const float*)w.occU, (const float*)w.occR, (const float*)w.coef, (const int32_t*)w.ku,
-                       (const int32_t*)w.ki, G);
+    launch_walk(grcn::loss_sum_rows, k.B, s, k, go, w.occU, w.occX, w.coef, w.ku, w.ki, G);
     return last_rc();
 }
 

@@ -14,10 +14,9 @@
 //
 // Layout: a d-wide row is one lane group of L = d / 4 float4 lanes (rsx_triplet.hpp's RowGeom).
 //
-// The loss.  Forward: loss_rows (a lane group a triplet, block partials in row order), finish
-//   (the partials in index order).  Backward: memsets, grad_rows (coefficient and user-row
-//   contribution of a triplet, the keys as int32), sum_rows: rsx_triplet.hpp's first-occurrence
-//   walk, which here also sends an item row's sum through the normalise Jacobian into gH.
+// The loss.  The protocol (one-score triplet, block partials, keys, the first-occurrence walk,
+//   workspace, argument checks) is rsx_triplet.hpp's; this file has the item row, the L2 term
+//   and the walk's epilogue, which sends an item row's sum through the normalise Jacobian into gH.
 // The graph.  One edge table [n, K], K = 2 M k: slots [m k, (m + 1) k) the learned list of
 //   modality m, slots [(M + m) k, ...) its original list.  The transpose is an index: the edge
 //   ids sorted by column (stable, built by the caller once per epoch) with a row pointer; the
@@ -48,24 +47,10 @@ __device__ __forceinline__ float4 item_row(const Args& a, int64_t i, int c) {
 }
 
 template <int D>
-struct Trip : TripIdx {
-    float4 ur, pr, nr;
-    float x;
-};
-
-template <int D>
-__device__ __forceinline__ void load_trip(const Args& a, int64_t b, int c, Trip<D>& t) {
-    constexpr int L = D / 4;
-    load_idx(a.trip, a.B, b, a.nu, a.ni, t);
-    t.ur = t.pr = t.nr = f4(0.f);
-    if (!t.ok) {  // uniform over the row's lane group
-        t.x = __builtin_nanf("");
-        return;
-    }
-    t.ur = ld4(a.E + t.u * D + c);
-    t.pr = item_row<D>(a, t.p, c);
-    t.nr = item_row<D>(a, t.n, c);
-    t.x = group_sum<L>(dot4(t.ur, t.pr)) - group_sum<L>(dot4(t.ur, t.nr));
+__device__ __forceinline__ void load_trip(const Args& a, int64_t b, int c, ScoreTrip& t) {
+    load_score_trip<D>(
+        a.trip, a.B, b, a.nu, a.ni, c, [&](int64_t u, int c) { return ld4(a.E + u * D + c); },
+        [&](int64_t i, int c) { return item_row<D>(a, i, c); }, t);
 }
 
 // part[block] = {sum softplus(-x), sum 1/2 (|u|^2 + |p|^2 + |n|^2)} over the block's triplets, in row order
@@ -75,7 +60,7 @@ __global__ __launch_bounds__(256) void loss_rows(Args a, float* __restrict__ par
     const RowGeom<D> r;
     float v[2] = {0.f, 0.f};
     if (r.b < a.B) {  // uniform over a row's lane group
-        Trip<D> t;
+        ScoreTrip t;
         load_trip<D>(a, r.b, r.c, t);
         v[0] = softplus_neg(t.x);
         const float sq = group_sum<L>(dot4(t.ur, t.ur)) + group_sum<L>(dot4(t.pr, t.pr)) +
@@ -108,13 +93,9 @@ __global__ __launch_bounds__(256) void grad_rows(Args a, const float* __restrict
     const int64_t b = r.b;
     const int c = r.c;
     if (b >= a.B) return;  // uniform over a row's lane group
-    Trip<D> t;
+    ScoreTrip t;
     load_trip<D>(a, b, c, t);
-    float ck = 0.f, s = 0.f;
-    if (t.ok) {
-        ck = -*go / (float)a.B * sigmoid_neg(t.x);
-        s = *go * a.reg / a.bs;
-    }
+    const float ck = bpr_coef(t, go, a.B), s = t.ok ? *go * a.reg / a.bs : 0.f;
     st4(occU + b * D + c, fma4(s, t.ur, mul4(ck, sub4(t.pr, t.nr))));
     if (c == 0) {
         coef[b] = ck;
@@ -122,8 +103,7 @@ __global__ __launch_bounds__(256) void grad_rows(Args a, const float* __restrict
     }
 }
 
-// The per-destination sums (rsx_triplet.hpp's walk).  Wave w < B: user occurrence w; else item
-// occurrence w - B of [positives; negatives].  An item row's sum g = sum(+-coef E[user]) +
+// The per-destination sums (rsx_triplet.hpp's walk).  An item row's sum g = sum(+-coef E[user]) +
 // count s row goes to gE[nu + key], and (g - hn <hn, g>) / max(|h|, eps), hn = h / max(|h|, eps),
 // to gH[key].
 template <int D>
@@ -131,39 +111,29 @@ __global__ __launch_bounds__(256) void sum_rows(Args a, const float* __restrict_
                                                 const float* __restrict__ coef, const int32_t* __restrict__ ku,
                                                 const int32_t* __restrict__ ki, float* __restrict__ gE,
                                                 float* __restrict__ gH) {
-    constexpr int L = RowGeom<D>::L;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), B = a.B;
-    if (w >= 3 * B) return;  // wave-uniform, as every branch on w, j and key below
-    const bool user = w < B;
-    const int32_t* __restrict__ keys = user ? ku : ki;
-    const int64_t n = user ? B : 2 * B, j = user ? w : w - B;
-    const int32_t key = keys[j];
-    if (key < 0 || !leads(keys, j, key, lane)) return;
-    const int g = lane / L, c = (lane % L) * 4;
+    constexpr int L = Walk<D>::L;
+    Walk<D> w;
+    if (!w.begin(ku, ki, a.B)) return;
+    const int c = w.c;
+    const int32_t key = w.key;
     float4 hn = f4(0.f), sp = f4(0.f);
     float inv = 0.f;
-    if (!user) {  // the item's own row, scaled by s: added once an occurrence
+    if (!w.user) {  // the item's own row, scaled by s: added once an occurrence
         const float4 h = ld4(a.H + (int64_t)key * D + c);
         inv = 1.f / fmaxf(sqrtf(group_sum<L>(dot4(h, h))), kNormEps);
         hn = mul4(inv, h);
         sp = mul4(*go * a.reg / a.bs, add4(hn, ld4(a.E + (a.nu + key) * D + c)));
     }
     float4 acc = f4(0.f);
-    for_each_match<D>(keys, j, n, key, lane, [&](int64_t mine) {
-        if (user) {
-            acc = add4(acc, ld4(occU + mine * D + c));
-        } else {
-            const int64_t b = mine < B ? mine : mine - B;
-            const float sgn = mine < B ? 1.f : -1.f;
-            acc = fma4(sgn * coef[b], ld4(a.E + (int64_t)ku[b] * D + c), acc);
-            acc = add4(acc, sp);
-        }
-    });
+    w.each([&](int64_t occ) { acc = add4(acc, ld4(occU + occ * D + c)); },
+           [&](int64_t b, float sgn) {
+               acc = fma4(sgn * coef[b], ld4(a.E + (int64_t)ku[b] * D + c), acc);
+               acc = add4(acc, sp);
+           });
     tree_rows<L>(acc);
     const float hg = group_sum<L>(dot4(hn, acc));  // every lane group holds the same sum now
-    if (g != 0) return;
-    if (user) {
+    if (w.g != 0) return;
+    if (w.user) {
         st4(gE + (int64_t)key * D + c, acc);
     } else {
         st4(gE + (a.nu + key) * D + c, acc);
@@ -187,9 +157,8 @@ inline int check(const rsx_lattice_args* a, void* ws, size_t ws_bytes, Args& k) 
 
 template <int D>
 int fwd(const Args& k, float* out, void* ws, hipStream_t s) {
-    constexpr int RPB = RowGeom<D>::RPB;
     const TripletWs w = carve(ws, k.B, D);
-    const int nblk = (int)((k.B + RPB - 1) / RPB);
+    const int nblk = rows_blocks<D>(k.B);
     hipLaunchKernelGGL(loss_rows<D>, dim3(nblk), dim3(256), 0, s, k, w.part);
     hipLaunchKernelGGL(finish, dim3(1), dim3(64), 0, s, (const float*)w.part, nblk, k.B, k.reg, k.bs, out);
     return last_rc();
@@ -197,16 +166,11 @@ int fwd(const Args& k, float* out, void* ws, hipStream_t s) {
 
 template <int D>
 int bwd(const Args& k, const float* go, float* gE, float* gH, void* ws, hipStream_t s) {
-    constexpr int RPB = RowGeom<D>::RPB;
     const TripletWs w = carve(ws, k.B, D);
-    hipError_t e;
-    if ((e = hipMemsetAsync(gE, 0, (size_t)(k.nu + k.ni) * D * sizeof(float), s)) != hipSuccess) return hip_rc(e);
-    if ((e = hipMemsetAsync(gH, 0, (size_t)k.ni * D * sizeof(float), s)) != hipSuccess) return hip_rc(e);
-    const int nblk = (int)((k.B + RPB - 1) / RPB);
-    hipLaunchKernelGGL(grad_rows<D>, dim3(nblk), dim3(256), 0, s, k, go, w.occU, w.coef, w.ku, w.ki);
-    hipLaunchKernelGGL(sum_rows<D>, dim3((unsigned)((3 * k.B + 3) / 4)), dim3(256), 0, s, k, go,
-                       (const float*)w.occU, (const float*)w.coef, (const int32_t*)w.ku, (const int32_t*)w.ki, gE,
-                       gH);
+    const int rc = zero_tables({{gE, (size_t)(k.nu + k.ni) * D}, {gH, (size_t)k.ni * D}}, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(grad_rows<D>, dim3(rows_blocks<D>(k.B)), dim3(256), 0, s, k, go, w.occU, w.coef, w.ku, w.ki);
+    launch_walk(sum_rows<D>, k.B, s, k, go, w.occU, w.coef, w.ku, w.ki, gE, gH);
     return last_rc();
 }
 

@@ -307,7 +307,8 @@ int ssl_bwd(const rsx_lgm_ssl_args* a, const float* go, float* gT1, float* gT2, 
     hipLaunchKernelGGL((ssl_tiles<D, 2>), dim3((unsigned)((N + 63) / 64), 1), dim3(256), 0, s, (const float*)w.M, N,
                        (const float*)w.n1, B, (B + 15) / 16 * 16, (const float*)w.lt, it, go, (const float*)w.nrm2,
                        same ? (const int32_t*)w.key : nullptr, (float*)nullptr, gT2);
-    if (gT1 != gT2) (void)hipMemsetAsync(gT1, 0, (size_t)N * D * sizeof(float), s);
+    const int rc = gT1 != gT2 ? zero_tables({{gT1, (size_t)N * D}}, s) : RSX_OK;
+    if (rc) return rc;
     hipLaunchKernelGGL(ssl_walk<D>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, (const float*)w.n1,
                        (const float*)w.occ, (const float*)w.M, (const float*)w.nrm2, (const int32_t*)w.key, B, it, go,
                        gT1, gT2);
@@ -488,6 +489,8 @@ inline int hg_check(int32_t H, int32_t ld, int32_t d) {
 }
 
 // ------------------------------------------------------------------ d. the loss
+// rsx_triplet.hpp's protocol (one-score triplet, block partials, keys, walk, workspace, checks)
+// on the rows of `all`; its own: AllRow, the Frobenius terms and the walk's five Jacobians.
 constexpr int kPartStride = 4, kCoef = 1;
 
 struct Loss {
@@ -511,24 +514,13 @@ struct AllRow {
 };
 
 template <int D>
-struct Trip : TripIdx {
-    float4 ur, pr, nr;
-    float x;
-};
-template <int D>
-__device__ __forceinline__ void load_trip(const Loss& a, int64_t b, int c, Trip<D>& t) {
-    constexpr int L = D / 4;
-    load_idx(a.trip, a.B, b, a.nu, a.ni, t);
-    t.ur = t.pr = t.nr = f4(0.f);
-    if (!t.ok) {  // uniform over the row's lane group
-        t.x = __builtin_nanf("");
-        return;
-    }
-    AllRow<D> w;
-    w.load(a, t.u, c), t.ur = w.all;
-    w.load(a, a.nu + t.p, c), t.pr = w.all;
-    w.load(a, a.nu + t.n, c), t.nr = w.all;
-    t.x = group_sum<L>(dot4(t.ur, t.pr)) - group_sum<L>(dot4(t.ur, t.nr));
+__device__ __forceinline__ void load_trip(const Loss& a, int64_t b, int c, ScoreTrip& t) {
+    const auto row = [&](int64_t r, int c) {
+        AllRow<D> w;
+        w.load(a, r, c);
+        return w.all;
+    };
+    load_score_trip<D>(a.trip, a.B, b, a.nu, a.ni, c, row, [&](int64_t i, int c) { return row(a.nu + i, c); }, t);
 }
 
 // part[block] = {sum softplus(-x), sum |u|^2, sum |p|^2, sum |n|^2} over the block's triplets
@@ -538,7 +530,7 @@ __global__ __launch_bounds__(256) void loss_rows(Loss a, float* __restrict__ par
     const RowGeom<D> r;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     if (r.b < a.B) {
-        Trip<D> t;
+        ScoreTrip t;
         load_trip<D>(a, r.b, r.c, t);
         v[0] = softplus_neg(t.x);
         v[1] = group_sum<L>(dot4(t.ur, t.ur));
@@ -574,13 +566,9 @@ __global__ __launch_bounds__(256) void loss_grad_rows(Loss a, const float* __res
                                                       int32_t* __restrict__ ku, int32_t* __restrict__ ki) {
     const RowGeom<D> r;
     if (r.b >= a.B) return;
-    Trip<D> t;
+    ScoreTrip t;
     load_trip<D>(a, r.b, r.c, t);
-    float ck = 0.f, s = 0.f;
-    if (t.ok) {
-        ck = -*go / (float)a.B * sigmoid_neg(t.x);
-        s = fro_scale(go, a.reg, a.B, nrm[0]);
-    }
+    const float ck = bpr_coef(t, go, a.B), s = t.ok ? fro_scale(go, a.reg, a.B, nrm[0]) : 0.f;
     st4(occU + r.b * D + r.c, fma4(s, t.ur, mul4(ck, sub4(t.pr, t.nr))));
     st4(allU + r.b * D + r.c, t.ur);
     if (r.c == 0) {
@@ -599,34 +587,25 @@ __global__ __launch_bounds__(256) void loss_sum_rows(Loss a, const float* __rest
                                                      float* __restrict__ gC, float* __restrict__ gMv,
                                                      float* __restrict__ gMt, float* __restrict__ gGv,
                                                      float* __restrict__ gGt) {
-    constexpr int L = RowGeom<D>::L;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), B = a.B;
-    if (w >= 3 * B) return;  // wave-uniform, as every branch on w, j and key below
-    const bool user = w < B;
-    const int32_t* __restrict__ keys = user ? ku : ki;
-    const int64_t n = user ? B : 2 * B, j = user ? w : w - B;
-    const int32_t key = keys[j];
-    if (key < 0 || !leads(keys, j, key, lane)) return;
-    const int g = lane / L, c = (lane % L) * 4;
-    const int64_t row = user ? key : a.nu + key;
+    constexpr int L = Walk<D>::L;
+    Walk<D> w;
+    if (!w.begin(ku, ki, a.B)) return;
+    const int c = w.c;
+    const int64_t row = w.user ? w.key : a.nu + w.key;
     AllRow<D> me;
     me.load(a, row, c);
-    const float4 spp = mul4(fro_scale(go, a.reg, B, nrm[1]), me.all), spn = mul4(fro_scale(go, a.reg, B, nrm[2]), me.all);
+    const float4 spp = mul4(fro_scale(go, a.reg, a.B, nrm[1]), me.all),
+                 spn = mul4(fro_scale(go, a.reg, a.B, nrm[2]), me.all);
     float4 acc = f4(0.f);
-    for_each_match<D>(keys, j, n, key, lane, [&](int64_t mine) {
-        if (user) {
-            acc = add4(acc, ld4(occU + mine * D + c));
-        } else {
-            const int64_t b = mine < B ? mine : mine - B;
-            acc = fma4(mine < B ? coef[b] : -coef[b], ld4(allU + b * D + c), acc);
-            acc = add4(acc, mine < B ? spp : spn);
-        }
-    });
+    w.each([&](int64_t occ) { acc = add4(acc, ld4(occU + occ * D + c)); },
+           [&](int64_t b, float sgn) {
+               acc = fma4(sgn * coef[b], ld4(allU + b * D + c), acc);
+               acc = add4(acc, sgn > 0.f ? spp : spn);
+           });
     tree_rows<L>(acc);
     const float4 jv = unit_jac<L>(me.nv, me.rv, acc), jt = unit_jac<L>(me.nt, me.rt, acc);
     const float4 jg = mul4(a.alpha, unit_jac<L>(me.ng, me.rg, acc));
-    if (g != 0) return;
+    if (w.g != 0) return;
     st4(gC + row * D + c, acc);
     st4(gMv + row * D + c, jv);
     st4(gMt + row * D + c, jt);
@@ -634,19 +613,15 @@ __global__ __launch_bounds__(256) void loss_sum_rows(Loss a, const float* __rest
     st4(gGt + row * D + c, jg);
 }
 
+// the shared workspace with allU as its extra row buffer (occX), then nrm [3]: the one piece a
+// backward reads from its forward
 struct LossWs {
     TripletWs t;
-    float *allU, *nrm;
-    size_t total;
+    float* nrm;
 };
 inline LossWs carve_loss(void* ws, int64_t B, int d) {
-    LossWs w;
-    w.t = carve_triplet(ws, B, d, kPartStride, kCoef);
-    Carver cv(ws);
-    cv.off = w.t.total;
-    w.allU = cv.take<float>((size_t)B * d * sizeof(float));
-    w.nrm = cv.take<float>(4 * sizeof(float));
-    w.total = cv.total();
+    LossWs w{carve_triplet(ws, B, d, kPartStride, kCoef, 1), nullptr};
+    w.nrm = w.t.cv.take<float>(4 * sizeof(float));
     return w;
 }
 
@@ -665,9 +640,8 @@ inline int loss_check(const rsx_lgm_loss_args* a, void* ws, size_t ws_bytes, Los
 
 template <int D>
 int loss_fwd(const Loss& k, float* out, void* ws, hipStream_t s) {
-    constexpr int RPB = RowGeom<D>::RPB;
     const LossWs w = carve_loss(ws, k.B, D);
-    const int nblk = (int)((k.B + RPB - 1) / RPB);
+    const int nblk = rows_blocks<D>(k.B);
     hipLaunchKernelGGL(loss_rows<D>, dim3(nblk), dim3(256), 0, s, k, w.t.part);
     hipLaunchKernelGGL(loss_finish, dim3(1), dim3(64), 0, s, (const float*)w.t.part, nblk, k.B, k.reg, out, w.nrm);
     return last_rc();
@@ -675,15 +649,14 @@ int loss_fwd(const Loss& k, float* out, void* ws, hipStream_t s) {
 
 template <int D>
 int loss_bwd(const Loss& k, const float* go, float* const (&gt)[5], void* ws, hipStream_t s) {
-    constexpr int RPB = RowGeom<D>::RPB;
     const LossWs w = carve_loss(ws, k.B, D);
-    const size_t bytes = (size_t)(k.nu + k.ni) * D * sizeof(float);
-    for (float* t : gt) (void)hipMemsetAsync(t, 0, bytes, s);
-    hipLaunchKernelGGL(loss_grad_rows<D>, dim3((unsigned)((k.B + RPB - 1) / RPB)), dim3(256), 0, s, k, go,
-                       (const float*)w.nrm, w.t.occU, w.allU, w.t.coef, w.t.ku, w.t.ki);
-    hipLaunchKernelGGL(loss_sum_rows<D>, dim3((unsigned)((3 * k.B + 3) / 4)), dim3(256), 0, s, k, go,
-                       (const float*)w.nrm, (const float*)w.t.occU, (const float*)w.allU, (const float*)w.t.coef,
-                       (const int32_t*)w.t.ku, (const int32_t*)w.t.ki, gt[0], gt[1], gt[2], gt[3], gt[4]);
+    const size_t n = (size_t)(k.nu + k.ni) * D;
+    const int rc = zero_tables({{gt[0], n}, {gt[1], n}, {gt[2], n}, {gt[3], n}, {gt[4], n}}, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loss_grad_rows<D>, dim3(rows_blocks<D>(k.B)), dim3(256), 0, s, k, go, (const float*)w.nrm,
+                       w.t.occU, w.t.occX, w.t.coef, w.t.ku, w.t.ki);
+    launch_walk(loss_sum_rows<D>, k.B, s, k, go, w.nrm, w.t.occU, w.t.occX, w.t.coef, w.t.ku, w.t.ki, gt[0], gt[1],
+                gt[2], gt[3], gt[4]);
     return last_rc();
 }
 
@@ -798,8 +771,7 @@ extern "C" int rsx_lgm_hgnn_rowdots(const float* X, const float* lat, int32_t H,
 }
 
 extern "C" size_t rsx_lgm_loss_ws_bytes(int64_t batch, int32_t d) {
-    if (batch < 1 || batch > kMaxBatch || (d != 64 && d != 128)) return 0;
-    return lgm::carve_loss(nullptr, batch, d).total;
+    return triplet_shape_ok(batch, d) ? lgm::carve_loss(nullptr, batch, d).t.cv.total() : 0;
 }
 
 extern "C" int rsx_lgm_loss_fwd(const rsx_lgm_loss_args* a, float* out, void* ws, size_t ws_bytes,

@@ -19,8 +19,9 @@
 //    A 64 x 64 output tile a block, 16 x 64 a wave, K in 32-wide slabs staged in LDS with the
 //    next slab's global loads in flight during the MFMAs.
 //  * normalize (F.normalize over the image branch's item rows), colsum (the bias gradients:
-//    block partial column sums, added in block order), the loss (rsx_triplet.hpp's
-//    first-occurrence walk, as freedom.hip) and the whole-table `result`.
+//    block partial column sums, added in block order), the loss (rsx_triplet.hpp's protocol:
+//    one-score triplet, block partials, keys, walk, workspace, checks; its own: the rep row
+//    and the id regulariser) and the whole-table `result`.
 //
 // Slopes are read off the sign of the saved f32 outputs (leaky(p) > 0 exactly when p > 0, the
 // slope being positive): no mask tensors.  No float atomics anywhere: two runs are bit-equal.
@@ -361,25 +362,12 @@ __device__ __forceinline__ float4 rep4(const LossArgs& a, int64_t row, int c) {
     return mul4(a.inv_m, v);
 }
 
+// the triplet on the rep rows of the user, the positive and the negative item
 template <int D>
-struct Trip : TripIdx {
-    float4 ur, pr, nr;  // the rep rows of the user, the positive and the negative item
-    float x;            // <u, p> - <u, n>
-};
-
-template <int D>
-__device__ __forceinline__ void load_trip(const LossArgs& a, int64_t b, int c, Trip<D>& t) {
-    constexpr int L = D / 4;
-    load_idx(a.trip, a.B, b, a.nu, a.ni, t);
-    t.ur = t.pr = t.nr = f4(0.f);
-    if (!t.ok) {  // uniform over the row's lane group
-        t.x = __builtin_nanf("");
-        return;
-    }
-    t.ur = rep4<D>(a, t.u, c);
-    t.pr = rep4<D>(a, a.nu + t.p, c);
-    t.nr = rep4<D>(a, a.nu + t.n, c);
-    t.x = group_sum<L>(dot4(t.ur, t.pr)) - group_sum<L>(dot4(t.ur, t.nr));
+__device__ __forceinline__ void load_trip(const LossArgs& a, int64_t b, int c, ScoreTrip& t) {
+    load_score_trip<D>(
+        a.trip, a.B, b, a.nu, a.ni, c, [&](int64_t u, int c) { return rep4<D>(a, u, c); },
+        [&](int64_t i, int c) { return rep4<D>(a, a.nu + i, c); }, t);
 }
 
 // part[block] = {sum softplus(-x), sum 2 |E_u|^2 + |E_p|^2 + |E_n|^2} over the block's triplets
@@ -389,7 +377,7 @@ __global__ __launch_bounds__(256) void loss_rows(LossArgs a, float* __restrict__
     const RowGeom<D> r;
     float v[2] = {0.f, 0.f};
     if (r.b < a.B) {  // uniform over a row's lane group
-        Trip<D> t;
+        ScoreTrip t;
         load_trip<D>(a, r.b, r.c, t);
         v[0] = softplus_neg(t.x);
         if (t.ok) {
@@ -428,9 +416,9 @@ __global__ __launch_bounds__(256) void loss_grad_rows(LossArgs a, const float* _
     const RowGeom<D> r;
     const int64_t b = r.b;
     if (b >= a.B) return;  // uniform over a row's lane group
-    Trip<D> t;
+    ScoreTrip t;
     load_trip<D>(a, b, r.c, t);
-    const float ck = t.ok ? -*go / (float)a.B * sigmoid_neg(t.x) : 0.f;
+    const float ck = bpr_coef(t, go, a.B);
     st4(occU + b * D + r.c, mul4(ck * a.inv_m, sub4(t.pr, t.nr)));
     st4(occR + b * D + r.c, mul4(a.inv_m, t.ur));
     if (r.c == 0) {
@@ -439,35 +427,21 @@ __global__ __launch_bounds__(256) void loss_grad_rows(LossArgs a, const float* _
     }
 }
 
-// The per-destination sums (rsx_triplet.hpp's walk).  Wave w < B: user occurrence w; else
-// item occurrence w - B of [positives; negatives].  G [n_users + n_items, D], zero-filled.
+// The per-destination sums (rsx_triplet.hpp's walk).  G [n_users + n_items, D], zero-filled.
 template <int D>
 __global__ __launch_bounds__(256) void loss_sum_rows(LossArgs a, const float* __restrict__ occU,
                                                      const float* __restrict__ occR, const float* __restrict__ coef,
                                                      const int32_t* __restrict__ ku, const int32_t* __restrict__ ki,
                                                      float* __restrict__ G) {
-    constexpr int L = RowGeom<D>::L;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), B = a.B;
-    if (w >= 3 * B) return;  // wave-uniform, as every branch on w, j and key below
-    const bool user = w < B;
-    const int32_t* __restrict__ keys = user ? ku : ki;
-    const int64_t n = user ? B : 2 * B, j = user ? w : w - B;
-    const int32_t key = keys[j];
-    if (key < 0 || !leads(keys, j, key, lane)) return;
-    const int g = lane / L, c = (lane % L) * 4;
+    Walk<D> w;
+    if (!w.begin(ku, ki, a.B)) return;
+    const int c = w.c;
     float4 acc = f4(0.f);
-    for_each_match<D>(keys, j, n, key, lane, [&](int64_t mine) {
-        if (user) {
-            acc = add4(acc, ld4(occU + mine * D + c));
-        } else {
-            const int64_t b = mine < B ? mine : mine - B;
-            acc = fma4(mine < B ? coef[b] : -coef[b], ld4(occR + b * D + c), acc);
-        }
-    });
-    tree_rows<L>(acc);
-    if (g != 0) return;
-    st4(G + (user ? (int64_t)key : a.nu + key) * D + c, acc);
+    w.each([&](int64_t occ) { acc = add4(acc, ld4(occU + occ * D + c)); },
+           [&](int64_t b, float sgn) { acc = fma4(sgn * coef[b], ld4(occR + b * D + c), acc); });
+    tree_rows<Walk<D>::L>(acc);
+    if (w.g != 0) return;
+    st4(G + (w.user ? (int64_t)w.key : a.nu + w.key) * D + c, acc);
 }
 
 // result = (x_v + x_t) / num_modal over the whole table (n4 float4)
@@ -480,24 +454,8 @@ __global__ __launch_bounds__(256) void write_result(const float* __restrict__ xv
     }
 }
 
-struct LossWs {
-    float *part, *occU, *occR, *coef;
-    int32_t *ku, *ki;
-    size_t total;
-};
-inline LossWs carve(void* ws, int64_t B, int d) {
-    LossWs w;
-    Carver cv(ws);
-    const int rpb = 256 / (d / 4);
-    w.part = cv.take<float>((size_t)((B + rpb - 1) / rpb) * kPartStride * sizeof(float));
-    w.occU = cv.take<float>((size_t)B * d * sizeof(float));
-    w.occR = cv.take<float>((size_t)B * d * sizeof(float));
-    w.coef = cv.take<float>((size_t)B * sizeof(float));
-    w.ku = cv.take<int32_t>((size_t)B * sizeof(int32_t));  // (256-byte pieces: match256's padding)
-    w.ki = cv.take<int32_t>((size_t)2 * B * sizeof(int32_t));
-    w.total = cv.total();
-    return w;
-}
+// one coefficient a triplet; occR is the workspace's extra row buffer (occX)
+inline TripletWs carve(void* ws, int64_t B, int d) { return carve_triplet(ws, B, d, kPartStride, 1, 1); }
 
 inline int loss_check(const rsx_mmgcn_loss_args* a, void* ws, size_t ws_bytes, LossArgs& k) {
     if (!a) return RSX_ERR_ARG;
@@ -516,9 +474,8 @@ inline int loss_check(const rsx_mmgcn_loss_args* a, void* ws, size_t ws_bytes, L
 
 template <int D>
 int loss_fwd(const LossArgs& k, float* out, float* result, void* ws, hipStream_t s) {
-    constexpr int RPB = RowGeom<D>::RPB;
-    const LossWs w = carve(ws, k.B, D);
-    const int nblk = (int)((k.B + RPB - 1) / RPB);
+    const TripletWs w = carve(ws, k.B, D);
+    const int nblk = rows_blocks<D>(k.B);
     hipLaunchKernelGGL(loss_rows<D>, dim3(nblk), dim3(256), 0, s, k, w.part);
     hipLaunchKernelGGL(loss_finish<D>, dim3(1), dim3(64), 0, s, (const float*)w.part, nblk, k.B, k.reg_weight,
                        k.pref_term, out);
@@ -533,14 +490,12 @@ int loss_fwd(const LossArgs& k, float* out, float* result, void* ws, hipStream_t
 
 template <int D>
 int loss_bwd(const LossArgs& k, const float* go, float* G, void* ws, hipStream_t s) {
-    constexpr int RPB = RowGeom<D>::RPB;
-    const LossWs w = carve(ws, k.B, D);
-    hipError_t e;
-    if ((e = hipMemsetAsync(G, 0, (size_t)(k.nu + k.ni) * D * sizeof(float), s)) != hipSuccess) return hip_rc(e);
-    const int nblk = (int)((k.B + RPB - 1) / RPB);
-    hipLaunchKernelGGL(loss_grad_rows<D>, dim3(nblk), dim3(256), 0, s, k, go, w.occU, w.occR, w.coef, w.ku, w.ki);
-    hipLaunchKernelGGL(loss_sum_rows<D>, dim3((unsigned)((3 * k.B + 3) / 4)), dim3(256), 0, s, k, (const float*)w.occU,
-                       (const float*)w.occR, (const float*)w.coef, (const int32_t*)w.ku, (const int32_t*)w.ki, G);
+    const TripletWs w = carve(ws, k.B, D);
+    const int rc = zero_tables({{G, (size_t)(k.nu + k.ni) * D}}, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(loss_grad_rows<D>, dim3(rows_blocks<D>(k.B)), dim3(256), 0, s, k, go, w.occU, w.occX, w.coef,
+                       w.ku, w.ki);
+    launch_walk(loss_sum_rows<D>, k.B, s, k, w.occU, w.occX, w.coef, w.ku, w.ki, G);
     return last_rc();
 }
 
@@ -662,8 +617,7 @@ int rsx_mmgcn_colsum(const float* g, int64_t n, int32_t n_cols, float* out, void
 }
 
 size_t rsx_mmgcn_loss_ws_bytes(int64_t batch, int32_t d) {
-    if (batch < 1 || batch > kMaxBatch || (d != 64 && d != 128)) return 0;
-    return mm::carve(nullptr, batch, d).total;
+    return triplet_ws_bytes(batch, d, mm::kPartStride, 1, 1);
 }
 
 int rsx_mmgcn_loss_fwd(const rsx_mmgcn_loss_args* a, float* out, float* result, void* ws, size_t ws_bytes,

@@ -139,6 +139,37 @@ def check_vs_f32(name, got, ref, tor):
     assert err <= bound, name
 
 
+LOSS_BATCHES = (1, 192, 300)
+
+
+def loss_triplets(rng, nu, ni, B):
+    """[3, B] triplets for a triplet loss's kernel test (nu > 13, ni > 9).  B = 1: the one drawn
+    triplet (one lane group of the block works; key lists of 1 and 2 entries).  Otherwise 40
+    repeats of user 11, 40 + 25 of item 7 as a positive and as a negative, and a triplet with the
+    last item.  B > 256 also has user 13 and item 9 only at indices >= 256 of their key lists
+    (users [B]; items [positives; negatives], 2 B): the wave that leads either sum scans a whole
+    256-key chunk without a match, and its walk starts at the second chunk."""
+    trip = np.stack([rng.integers(0, nu, B), rng.integers(0, ni, B), rng.integers(0, ni, B)]).astype(np.int64)
+    if B == 1:
+        return trip
+    trip[0, rng.permutation(B)[:40]] = 11  # 40 repeats of one user
+    trip[1, rng.permutation(B)[:40]] = 7  # and of one hot item, among the positives
+    trip[2, rng.permutation(B)[:25]] = 7  # and among the negatives
+    trip[:, 5] = (0, ni - 1, 0)
+    assert (trip[0] == 11).sum() >= 40 and (trip[1] == 7).sum() >= 40
+    if B > 256:
+        trip[0][trip[0] == 13] = 11
+        trip[1:][trip[1:] == 9] = 7
+        three = [258, B - 20, B - 1]  # triplets past the first chunk
+        trip[0, three] = 13
+        trip[1, [three[0], three[2]]] = 9  # item keys 258 and B - 1 ...
+        trip[2, three[1]] = 9  # ... and 2 B - 20
+        items = np.concatenate([trip[1], trip[2]])
+        assert np.flatnonzero(trip[0] == 13).tolist() == three
+        assert np.flatnonzero(items == 9).tolist() == [258, B - 1, 2 * B - 20]
+    return trip
+
+
 def take_first(c):
     """The first value of every hyper-parameter a Config lists several of; returns `c`."""
     for k in c["hyper_parameters"]:

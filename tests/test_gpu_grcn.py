@@ -23,8 +23,8 @@ import torch
 import grcn_kernels_ref as K
 import grcn_ref as R
 import test_grcn_cpu as T
-from helpers import (assert_same_run, check_eval, check_params, check_vs_f32, dev, loaders, make_model,
-                     quick_start_case, record_batches, train_epochs, write_dataset)
+from helpers import (LOSS_BATCHES, assert_same_run, check_eval, check_params, check_vs_f32, dev, loaders, loss_triplets,
+                     make_model, quick_start_case, record_batches, train_epochs, write_dataset)
 
 pytestmark = pytest.mark.gpu
 NAMES = T.NAMES
@@ -253,19 +253,21 @@ def test_step_chain_on_the_hub_graph(cuda, dc, M):
 
 
 # ----------------------------------------------------------------------- loss
-@pytest.mark.parametrize("dx,dc,M,ld", [(64, 64, 2, 256), (64, 64, 1, 128), (64, 64, 1, 256), (128, 64, 2, 256),
-                                        (64, 128, 1, 256)])
-def test_loss_value_gradients_and_result(cuda, dx, dc, M, ld):
+LOSS_SHAPES = [(64, 64, 2, 256), (64, 64, 1, 128), (64, 64, 1, 256), (128, 64, 2, 256), (64, 128, 1, 256)]
+
+
+LOSS_CASES = [s + (B,) for B in LOSS_BATCHES for s in LOSS_SHAPES]
+
+
+# (the cases at B = 192 keep the ids they had before the batch became a parameter)
+@pytest.mark.parametrize("dx,dc,M,ld,B", LOSS_CASES,
+                         ids=["-".join(map(str, k[:4] if k[4] == 192 else k)) for k in LOSS_CASES])
+def test_loss_value_gradients_and_result(cuda, dx, dc, M, ld, B):
     from rsx import grcn as G
 
     rng = np.random.default_rng(3)
-    nu, ni, B = 70, 50, 192
-    trip = np.stack([rng.integers(0, nu, B), rng.integers(0, ni, B), rng.integers(0, ni, B)]).astype(np.int64)
-    trip[0, rng.permutation(B)[:40]] = 11  # 40 repeats of one user
-    trip[1, rng.permutation(B)[:40]] = 7  # and of one hot item, among the positives
-    trip[2, rng.permutation(B)[:25]] = 7  # and among the negatives
-    trip[:, 5] = (0, 49, 0)
-    assert (trip[0] == 11).sum() >= 40 and (trip[1] == 7).sum() >= 40
+    nu, ni = 70, 50
+    trip = loss_triplets(rng, nu, ni, B)
     n = nu + ni
     f32 = lambda shape, s: (rng.standard_normal(shape) * s).astype(np.float32)  # noqa: E731
     tabs = dict(id=f32((n, dx), 0.4), E=f32((n, dx), 0.3))

@@ -18,8 +18,8 @@ import pytest
 import torch
 
 import mmgcn_ref as R
-from helpers import (assert_same_run, check_eval, check_params, check_vs_f32, coo_sorted, csr_to_sorted, dev, loaders,
-                     make_model, quick_start_case, record_batches, train_epochs, write_dataset)
+from helpers import (LOSS_BATCHES, assert_same_run, check_eval, check_params, check_vs_f32, coo_sorted, csr_to_sorted, dev,
+                     loaders, loss_triplets, make_model, quick_start_case, record_batches, train_epochs, write_dataset)
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(64, 5), (64, 65), (128, 37), (64, 1001)]
@@ -176,14 +176,10 @@ def test_colsum_is_ordered(cuda):
 
 
 # ----------------------------------------------------------------------- loss
-def _loss_case(d, mods, seed=3):
+def _loss_case(d, mods, B, seed=3):
     rng = np.random.default_rng(seed)
-    nu, ni, B = 70, 50, 192
-    trip = np.stack([rng.integers(0, nu, B), rng.integers(0, ni, B), rng.integers(0, ni, B)]).astype(np.int64)
-    trip[0, rng.permutation(B)[:40]] = 11  # 40 repeats of one user
-    trip[1, rng.permutation(B)[:40]] = 7  # and of one hot item, among the positives
-    trip[2, rng.permutation(B)[:25]] = 7  # and among the negatives
-    trip[:, 5] = (0, 49, 0)
+    nu, ni = 70, 50
+    trip = loss_triplets(rng, nu, ni, B)
     tabs = {m: (rng.standard_normal((nu + ni, d)) * 0.4).astype(np.float32) for m in mods}
     E = (rng.standard_normal((nu + ni, d)) * 0.3).astype(np.float32)
     return nu, ni, trip, tabs, E
@@ -200,11 +196,14 @@ def _run_loss(cuda, nu, trip, tabs, E, reg_weight, pref_term, result=None):
     return loss.item(), c(keep["terms"]), {m: c(x.grad) for m, x in t.items()}
 
 
-@pytest.mark.parametrize("d", [64, 128])
-@pytest.mark.parametrize("mods", [("v", "t"), ("v",), ("t",)], ids="".join)
-def test_loss_value_gradients_and_result(cuda, d, mods):
-    nu, ni, trip, tabs, E = _loss_case(d, mods)
-    assert (trip[0] == 11).sum() >= 40 and (trip[1] == 7).sum() >= 40
+LOSS_CASES = [(mods, d, B) for B in LOSS_BATCHES for d in (64, 128) for mods in (("v", "t"), ("v",), ("t",))]
+
+
+# (the cases at B = 192 keep the ids they had before the batch became a parameter)
+@pytest.mark.parametrize("mods,d,B", LOSS_CASES,
+                         ids=["".join(m) + f"-{d}" + ("" if B == 192 else f"-{B}") for m, d, B in LOSS_CASES])
+def test_loss_value_gradients_and_result(cuda, d, mods, B):
+    nu, ni, trip, tabs, E = _loss_case(d, mods, B)
     pref = np.random.default_rng(1).standard_normal((nu, 8)).astype(np.float32)
     res = {}
     for dtype in (torch.float64, torch.float32):

@@ -7,7 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import assert_same_run, check_params, check_vs_f32, take_first, write_dataset
+from helpers import (LOSS_BATCHES, assert_same_run, check_params, check_vs_f32, loss_triplets, take_first,
+                     write_dataset)
 
 
 def _ref():
@@ -93,6 +94,28 @@ def test_write_dataset_writes_the_files_it_was_given(tmp_path, which):
     gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gold_small.inter")
     with open(os.path.join(path, "baby", "baby.inter"), "rb") as f, open(gold, "rb") as g:
         assert f.read() == g.read()
+
+
+def test_loss_triplets_plant_what_the_loss_tests_rely_on():
+    """The batches of the MMGCN and GRCN loss tests, at their table sizes: B = 192 is the batch the
+    tests always had; B = 300 has a user and an item first met past the first 256 keys of their
+    lists, and still leaves a table row that no triplet touches."""
+    nu, ni = 70, 50
+    assert LOSS_BATCHES == (1, 192, 300)
+    for B in LOSS_BATCHES:
+        trip = loss_triplets(np.random.default_rng(3), nu, ni, B)
+        assert trip.shape == (3, B) and trip.dtype == np.int64
+        assert trip[0].min() >= 0 and trip[0].max() < nu and trip[1:].min() >= 0 and trip[1:].max() < ni
+        rows = np.unique(np.concatenate([trip[0], nu + trip[1], nu + trip[2]]))
+        assert rows.size < nu + ni
+    rng = np.random.default_rng(3)  # B = 192, as the tests drew it before the batch became a parameter
+    old = np.stack([rng.integers(0, nu, 192), rng.integers(0, ni, 192), rng.integers(0, ni, 192)]).astype(np.int64)
+    old[0, rng.permutation(192)[:40]] = 11
+    old[1, rng.permutation(192)[:40]] = 7
+    old[2, rng.permutation(192)[:25]] = 7
+    old[:, 5] = (0, 49, 0)
+    assert np.array_equal(loss_triplets(np.random.default_rng(3), nu, ni, 192), old)
+    assert np.flatnonzero(trip[0] == 13).min() >= 256 and np.flatnonzero(np.concatenate([trip[1], trip[2]]) == 9).min() >= 256
 
 
 def test_take_first():

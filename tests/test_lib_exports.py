@@ -70,6 +70,35 @@ def test_comm_unique_id_size():
     assert L.lib().rsx_comm_unique_id_bytes() == 128
 
 
+# rsx_*_ws_bytes(B, d) at B = 1, 67, 2048, 65536, as the library returned them before the losses
+# shared one workspace layout (csrc/rsx_triplet.hpp's carve_triplet): d = 64, then d = 128
+TRIPLET_WS_BYTES = {
+    "rsx_freedom_ws_bytes": ([1280, 19712, 575488, 18415616], [1536, 36864, 1101824, 35258368]),
+    "rsx_lattice_ws_bytes": ([1280, 19200, 558080, 17858560], [1536, 36352, 1083392, 34668544]),
+    "rsx_lgm_loss_ws_bytes": ([1792, 36608, 1083648, 34668800], [2304, 70912, 2134272, 68288768]),
+    "rsx_mmgcn_loss_ws_bytes": ([1536, 36352, 1082368, 34635776], [2048, 70656, 2131968, 68222976]),
+}
+# rsx_grcn_loss_ws_bytes(B, width) at the same B: width = 128, 192, 256
+GRCN_WS_BYTES = {128: [3072, 71936, 2139136, 68420608], 192: [3584, 106240, 3187712, 101975040],
+                 256: [4096, 140544, 4236288, 135529472]}
+
+
+def test_triplet_loss_workspace_sizes_are_pinned():
+    """The five triplet losses' workspace sizes are the recorded ones for every shape, and 0
+    for a batch or a width the losses do not take (host-only functions: no GPU)."""
+    lib = L.lib()
+    batches = (1, 67, 2048, 65536)
+    for name, per_d in TRIPLET_WS_BYTES.items():
+        f = getattr(lib, name)
+        for d, want in zip((64, 128), per_d):
+            assert [f(B, d) for B in batches] == want, (name, d)
+        assert [f(0, 64), f(65537, 64), f(67, 32)] == [0, 0, 0], name
+    f = lib.rsx_grcn_loss_ws_bytes
+    for width, want in GRCN_WS_BYTES.items():
+        assert [f(B, width) for B in batches] == want, width
+    assert [f(0, 128), f(65537, 128), f(67, 32)] == [0, 0, 0]
+
+
 def test_schedule_host_splits_hub_rows():
     lib = L.lib()
     deg = np.array([0, 3, 32, 33, 100, 0, 1])
