@@ -1826,6 +1826,64 @@ int rsx_grcn_loss_fwd(const rsx_grcn_loss_args* a, float* out, float* result, in
 int rsx_grcn_loss_bwd(const rsx_grcn_loss_args* a, const float* go, float* g_id, float* g_v, float* g_t, float* gE,
                       float* gpv, float* gpt, void* ws, size_t ws_bytes, rsx_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* DualGNN: modality mix, user graph, loss (dualgnn.hip)                      */
+/* ------------------------------------------------------------------------ */
+/*
+ * Every call here is d = 64 (dim_latent is hard-coded in the reference, src/models/dualgnn.py:47;
+ * else RSX_ERR_UNSUPPORTED), f32, deterministic and free of atomics; tables 16-byte aligned
+ * (else RSX_ERR_ARG); caller-owned buffers, no allocation or synchronisation; stream-ordered,
+ * graph-capturable.  n = n_users + n_items < 2^31.
+ *
+ * The mix (dualgnn.py:146-170, with the in-place alias `representation = v_rep; representation
+ * += t_rep`), one pass over xv, xt [n, 64]; weight_u [n_users, 2]:
+ *   user rows   user_rep[u] = w0 (v + t) + w1 t            -> user_rep [n_users, 64]
+ *   item rows   v + t                                      -> rows [n_users, n) of result [n, 64]
+ * One table NULL (one modality): its rows are copied through and weight_u is not applied.
+ * rsx_dualgnn_mix_bwd, from g_user_rep [n_users, 64] and the item rows of g_result [n, 64]:
+ *   g_v, g_t [n, 64]: user rows w0 g and (w0 + w1) g, item rows g for both;
+ *   g_weight_u[u] = (<g, v + t>, <g, t>) + *go 2 reg_weight / (2 n_users) weight_u[u]
+ * (the regulariser mean(weight_u^2) of :193 in the same pass; one modality: that term alone).
+ * go: the upstream gradient of the loss, a device word.
+ */
+int rsx_dualgnn_mix_fwd(const float* xv, const float* xt, const float* weight_u, int64_t n_users, int64_t n_items,
+                        int32_t d, float* user_rep, float* result, rsx_stream_t stream);
+int rsx_dualgnn_mix_bwd(const float* g_user_rep, const float* g_result, const float* xv, const float* xt,
+                        const float* weight_u, const float* go, float reg_weight, int64_t n_users, int64_t n_items,
+                        int32_t d, float* g_v, float* g_t, float* g_weight_u, rsx_stream_t stream);
+/*
+ * The user graph (dualgnn.py:172-173, 259-266): out[u] = user_rep[u] + sum_{j < k} W[u, j]
+ * user_rep[idx[u, j]], j ascending; idx int32 [n_users, k], W [n_users, k], 1 <= k <= 64 (else
+ * RSX_ERR_UNSUPPORTED).  An index outside [0, n_users) contributes nothing.  out must not be
+ * user_rep.  The backward is g + P^T g on rsx_spmm over the transposed lists.
+ */
+int rsx_dualgnn_ugraph_fwd(const float* user_rep, const int32_t* idx, const float* W, int64_t n_users, int32_t k,
+                           int32_t d, float* out, rsx_stream_t stream);
+/*
+ * The loss (dualgnn.py:175-197) on result [n, 64] (user row u, item row n_users + i), with x_b
+ * the BPR score difference:
+ *   out = {bpr + reg, bpr, reg},  bpr = mean softplus(-x_b) / ln 2   (-mean log2 sigmoid)
+ *   reg = reg_weight (sum_b |pref_v[u_b]|^2 / (batch 64) + sum_b |pref_t[u_b]|^2 / (batch 64))
+ *         + reg_weight mean(weight_u^2) + reg_weight mean(weight_i^2)
+ * pref_v, pref_t [n_users, 64] (either may be NULL), weight_u [n_users, 2], weight_i [n_items, 2].
+ * The backward writes EVERY row of g_result [n, 64] (zero off the batch, repeated rows summed by
+ * the first-occurrence walk), of g_pref_v, g_pref_t [n_users, 64] (2 reg_weight / (batch 64)
+ * count(u) pref_m[u], count the user's occurrences in the batch) and g_weight_i = 2 reg_weight /
+ * (2 n_items) weight_i; weight_u's term is rsx_dualgnn_mix_bwd's.  go: the upstream gradient, a
+ * device word.  1 <= batch <= 65536; ws >= rsx_dualgnn_loss_ws_bytes(batch, d) (0: unsupported).
+ */
+typedef struct rsx_dualgnn_loss_args {
+    const float *result, *pref_v, *pref_t, *weight_u, *weight_i;
+    const int64_t* triplets; /* [3, batch] users, positives, negatives (item ids, not offset) */
+    int64_t n_users, n_items, batch;
+    int32_t d;
+    float reg_weight;
+} rsx_dualgnn_loss_args;
+size_t rsx_dualgnn_loss_ws_bytes(int64_t batch, int32_t d);
+int rsx_dualgnn_loss_fwd(const rsx_dualgnn_loss_args* a, float* out, void* ws, size_t ws_bytes, rsx_stream_t stream);
+int rsx_dualgnn_loss_bwd(const rsx_dualgnn_loss_args* a, const float* go, float* g_result, float* g_pref_v,
+                         float* g_pref_t, float* g_weight_i, void* ws, size_t ws_bytes, rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,11 @@ class GrcnLossArgs(C.Structure):
                 ("pad0", I32)]
 
 
+class DualgnnLossArgs(C.Structure):
+    _fields_ = [("result", P), ("pref_v", P), ("pref_t", P), ("weight_u", P), ("weight_i", P), ("triplets", P),
+                ("n_users", I64), ("n_items", I64), ("batch", I64), ("d", I32), ("reg_weight", F32)]
+
+
 class LatticeGraph(C.Structure):
     _fields_ = [("n", I64), ("k", I32), ("n_mod", I32), ("f", I32), ("lam", F32), ("F", P * 2), ("idx", P * 2),
                 ("oidx", P * 2), ("oval", P * 2), ("modal_weight", P), ("w", P), ("invn", P * 2), ("a", P * 2),
@@ -331,6 +336,12 @@ def _declare(lib):
         "rsx_grcn_loss_ws_bytes": (C.c_size_t, [I64, I32]),
         "rsx_grcn_loss_fwd": (C.c_int, [C.POINTER(GrcnLossArgs), P, P, I64, P, C.c_size_t, P]),
         "rsx_grcn_loss_bwd": (C.c_int, [C.POINTER(GrcnLossArgs), P, P, P, P, P, P, P, P, C.c_size_t, P]),
+        "rsx_dualgnn_mix_fwd": (C.c_int, [P, P, P, I64, I64, I32, P, P, P]),
+        "rsx_dualgnn_mix_bwd": (C.c_int, [P, P, P, P, P, P, F32, I64, I64, I32, P, P, P, P]),
+        "rsx_dualgnn_ugraph_fwd": (C.c_int, [P, P, P, I64, I32, I32, P, P]),
+        "rsx_dualgnn_loss_ws_bytes": (C.c_size_t, [I64, I32]),
+        "rsx_dualgnn_loss_fwd": (C.c_int, [C.POINTER(DualgnnLossArgs), P, P, C.c_size_t, P]),
+        "rsx_dualgnn_loss_bwd": (C.c_int, [C.POINTER(DualgnnLossArgs), P, P, P, P, P, P, C.c_size_t, P]),
         "rsx_cpu_spmm": (C.c_int, [P, P, P, I64, P, I32, P]),
         "rsx_cpu_propagate_mean": (C.c_int, [P, P, P, I64, P, I32, I32, P]),
         "rsx_cpu_layergcn_forward": (C.c_int, [P, P, P, I64, P, I32, I32, P, P, P]),
@@ -380,6 +391,8 @@ EXPORTED = ["rsx_version", "rsx_csr_schedule_host", "rsx_csr_schedule_rebind", "
             "rsx_mmgcn_loss_fwd", "rsx_mmgcn_loss_bwd",
             "rsx_grcn_hub_degree", "rsx_grcn_attn_fwd", "rsx_grcn_attn_bwd", "rsx_grcn_refine_fwd", "rsx_grcn_edge_dots",
             "rsx_grcn_refine_bwd", "rsx_grcn_leaky_bwd", "rsx_grcn_loss_ws_bytes", "rsx_grcn_loss_fwd", "rsx_grcn_loss_bwd",
+            "rsx_dualgnn_mix_fwd", "rsx_dualgnn_mix_bwd", "rsx_dualgnn_ugraph_fwd", "rsx_dualgnn_loss_ws_bytes",
+            "rsx_dualgnn_loss_fwd", "rsx_dualgnn_loss_bwd",
             "rsx_cpu_spmm", "rsx_cpu_propagate_mean", "rsx_cpu_layergcn_forward", "rsx_cpu_layergcn_backward",
             "rsx_cpu_bpr", "rsx_cpu_fullsort_topk", "rsx_cpu_adam", "rsx_cpu_gcn_step_ws_floats", "rsx_cpu_gcn_step"]
 

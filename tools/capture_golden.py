@@ -13,13 +13,15 @@ modifies a reference file:
    `src/models/mgcn.py:59,69`, `src/models/lattice.py:76,87`);
 4. `torch_scatter.scatter_add` is restated with `index_add_` (`src/utils/utils.py:140`).
 
-GRCN and MMGCN add a fifth for their own captures: `torch_geometric` as far as `src/models/grcn.py`
-and `src/models/mmgcn.py` use it (`_install_pyg_shim`).
+GRCN, MMGCN and DualGNN add a fifth for their own captures: `torch_geometric` as far as
+`src/models/grcn.py`, `src/models/mmgcn.py` and `src/models/dualgnn.py` use it (`_install_pyg_shim`).
+DualGNN's capture also runs the reference's user-graph generator and moves `result_embed` out of
+the CPU model's parameters (`_dualgnn_user_graph`, `_dualgnn_model`).
 
 Outputs are small `.npz` files under `tests/golden/` (data only: inputs and the
 reference's outputs). The reference itself never travels to the GPU box.
 
-Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn]
+Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn | dualgnn]
 """
 from __future__ import annotations
 
@@ -1465,10 +1467,248 @@ def capture_mmgcn(out_dir):
         assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
 
 
+DUALGNN_ROWS = dict(rep=4, grad=2, param=4, const=8, epoch=8, last=4)  # row strides of the stored tables
+DUALGNN_SEEDS = dict(v=41, t=42)  # feature seeds at which the capture's pre-activation margin holds
+DUALGNN_GEN = os.path.join(os.path.dirname(REF), "preprocessing", "dualgnn-gen-u-u-matrix.py")
+
+
+def _flat2(a):
+    """weight_u / weight_i [n, 2, 1] as [n, 2]; every other array as it is."""
+    return a.reshape(a.shape[0], -1) if a.ndim > 2 else a
+
+
+def _dualgnn_user_graph(inter_path: str, out_path: str):
+    """The reference's generator on the training rows of `inter_path`: its own gen_user_matrix
+    (the script is loaded by path: its name has hyphens; its imports the harness lacks get empty
+    stand-ins) and the top-200 cut of its __main__ block, restated here because that block is
+    not a function.  Writes the dict as the reference does; returns it."""
+    import importlib.util
+
+    import pandas as pd
+
+    try:
+        import tqdm  # noqa: F401
+    except ImportError:
+        tq = types.ModuleType("tqdm")
+
+        class _Bar:
+            def __init__(self, *a, **k):
+                pass
+
+            def update(self, n=1):
+                pass
+
+            def close(self):
+                pass
+
+        tq.tqdm = _Bar
+        sys.modules["tqdm"] = tq
+    spec = importlib.util.spec_from_file_location("dualgnn_gen_u_u_matrix", DUALGNN_GEN)
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    df = pd.read_csv(inter_path, sep="\t")
+    num_user = len(pd.unique(df["userID"]))
+    train = df[df["x_label"] == 0][["userID", "itemID"]].to_numpy()
+    graph = gen.gen_user_matrix(train, num_user)
+    d = {}
+    for i in range(num_user):
+        num = int(len(torch.nonzero(graph[i])))
+        top = torch.topk(graph[i], min(num, 200))
+        d[i] = [top.indices.numpy().tolist(), top.values.numpy().tolist()]
+    np.save(out_path, d, allow_pickle=True)
+    return d, graph.numpy()
+
+
+def _dualgnn_model():
+    """The reference's DualGNN on the CPU.  Its constructor leaves `result_embed` registered as a
+    float64 Parameter there (`.to(device)` of the same device returns the Parameter itself), and
+    the first forward then cannot assign a tensor under that name; on a GPU it is a plain tensor.
+    It is popped from `_parameters` and set back as a plain tensor before the Trainer and its
+    optimiser are made.  Nothing in the reference is edited."""
+    from utils.utils import init_seed, get_model
+    from common.trainer import Trainer
+
+    config, train, valid, test = _load("DualGNN", "baby", GRCN_OVERRIDES)
+    hp = _select_hparams(config)
+    init_seed(config["seed"])
+    train.pretrain_setup()
+    model = get_model("DualGNN")(config, train)
+    emb = model._parameters.pop("result_embed")
+    assert emb.dtype == torch.float64
+    model.result_embed = emb.detach().clone()
+    assert "result_embed" not in dict(model.named_parameters())
+    return config, hp, train, valid, test, model, Trainer(config, model)
+
+
+def capture_dualgnn(out_dir):
+    """DualGNN (reference src/models/dualgnn.py) on the small graph, 48-wide image and 32-wide text
+    features: seed 999, the YAML's sizes, learning_rate and reg_weight 0.001, batches of 512; the
+    user graph from the reference's own generator.  torch_geometric is the shim above.
+    dualgnn_step0_small.npz: the first two steps: triplets, loss / bpr / reg (bpr and reg in
+    float64 on the model's own tensors; they have to account for the loss), step 0's x_hat of
+    either modality (taken before the in-place add), user_rep, result and every gradient, the
+    parameters after either step; the pre-activation margin (below).
+    dualgnn_small.npz: the user lists as flat arrays, the two epochs' sampled lists and weights,
+    the initial parameters and result_embed, the features, two epochs through the reference's
+    Trainer with the parameters after each, the evaluation of the initial table and of the last
+    epoch.
+    The capture fails unless at step 0 every leaky_relu pre-activation of the reference (the
+    output of either MLP) is farther from zero than twice the largest difference, on that tensor,
+    between the reference's float32 pre-activation and the float64 restatement's
+    (tests/dualgnn_ref.py).  Both tensors are functions of the feature seeds on every row."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import dualgnn_ref as R
+
+    shutil.rmtree(os.path.join(DATA_ROOT, "baby"), ignore_errors=True)
+    df = synth.amazon_like(400, 200, 4000, seed=7)
+    synth.write_inter(df, DATA_ROOT, "baby")
+    n_items = int(df.itemID.max()) + 1
+    base = os.path.join(DATA_ROOT, "baby")
+    np.save(os.path.join(base, "image_feat_raw.npy"), synth.features(n_items, 48, seed=DUALGNN_SEEDS["v"]))
+    np.save(os.path.join(base, "text_feat_raw.npy"), synth.features(n_items, 32, seed=DUALGNN_SEEDS["t"]))
+    lists, _ = _dualgnn_user_graph(os.path.join(base, "baby.inter"), os.path.join(base, "user_graph_dict.npy"))
+    _install_pyg_shim()
+    S = DUALGNN_ROWS
+
+    # ---- pass 1: the first two steps
+    config, hp, train, valid, test, model, trainer = _dualgnn_model()
+    nu, ni = model.n_users, model.n_items
+    names = tuple(n for n, _ in model.named_parameters())
+    assert names == R.names(), names
+    # After its first forward the reference's model also holds either preference as `v_preference`
+    # / `t_preference` (dualgnn.py:147,150 assign the Parameter to an attribute of the model, which
+    # registers it), and named_parameters() then lists it under that name.  The fixtures keep the
+    # names of the constructed model throughout.
+    fixed = lambda mdl: [(n, p) for n, p in zip(names, [q for _, q in mdl.named_parameters()])]  # noqa: E731
+    params = fixed(model)
+    init = {n: p.detach().numpy().copy() for n, p in params}
+    result0 = model.result_embed.numpy().copy()
+    feats32 = {"v": model.v_feat, "t": model.t_feat}
+    ei = model.edge_index.numpy()
+    E = ei.shape[1] // 2
+    train_u, train_i = ei[0, :E], ei[1, :E] - nu
+    A64 = R.sym_operator(train_u, train_i, nu, ni)
+    taps = {}
+    for m, g in (("v", model.v_gcn), ("t", model.t_gcn)):
+        g.MLP.register_forward_hook(lambda _m, _i, o, key=("pre", m): taps.__setitem__(key, o.detach().clone()))
+        g.register_forward_hook(lambda _m, _i, o, key=("x_hat", m): taps.__setitem__(key, o[0].detach().clone()))
+    model.user_graph.register_forward_hook(lambda _m, i, _o: taps.__setitem__("user_rep", i[0].detach().clone()))
+    model.pre_epoch_processing()
+    idx0 = np.asarray(model.epoch_user_graph, dtype=np.int64)
+    W0 = model.user_weight_matrix.numpy().copy()
+    out = {"n_users": np.int64(nu), "n_items": np.int64(ni)}
+    P64 = R.cast({n: torch.from_numpy(v) for n, v in init.items()}, torch.float64)
+    f64 = {m: f.double() for m, f in feats32.items()}
+    model.train()
+    it = iter(train)
+    for step in range(2):
+        batch = next(it)
+        trip = batch.clone()  # the reference's forward offsets the item rows of the batch in place
+        trainer.optimizer.zero_grad()
+        loss = model.calculate_loss(batch)
+        loss.backward()
+        pre = f"step{step}_"
+        rep = model.result_embed.detach()
+        if step == 0:
+            keep = {}
+            with torch.no_grad():
+                R.forward(P64, f64, A64, idx0, torch.from_numpy(W0).double(), nu, keep)
+            margin, worst = np.inf, 0.0
+            for m in R.MODS:
+                p32, p64 = taps[("pre", m)], keep[m]["pre"]
+                diff = float((p32.double() - p64).abs().max())
+                near = float(p32.abs().min())
+                assert near > 2 * diff, f"{m}: a pre-activation at {near:.3e}, reference vs restatement {diff:.3e}: pick other feature seeds"
+                margin, worst = min(margin, near / diff), max(worst, diff)
+                out[f"step0_preact_min.{m}"] = np.float64(near)
+                out[f"step0_preact_thr.{m}"] = np.float64(2 * diff)
+            print(f"pre-activations: smallest |pre| / (reference - restatement) = {margin:.1f} (needs > 2), largest "
+                  f"difference {worst:.3e}")
+            out["step0_x_hat_v"] = taps[("x_hat", "v")].numpy()[::S["rep"]].copy()
+            out["step0_x_hat_t"] = taps[("x_hat", "t")].numpy()[::S["rep"]].copy()
+            out["step0_user_rep"] = taps["user_rep"].numpy()[::S["rep"]].copy()
+            out["step0_result"] = rep.numpy()[::S["rep"]].copy()
+        u, p, n = trip[0], trip[1] + nu, trip[2] + nu
+        r64 = rep.double()
+        bpr = torch.nn.functional.softplus(-((r64[u] * r64[p]).sum(1) - (r64[u] * r64[n]).sum(1))).mean() / np.log(2.0)
+        reg = float(model.reg_weight) * sum((t.detach().double() ** 2).mean() for t in (
+            model.v_gcn.preference[u], model.t_gcn.preference[u], model.weight_u, model.weight_i))
+        assert abs(loss.item() - bpr.item() - reg.item()) <= 3e-6 * abs(loss.item()), (loss.item(), bpr.item(), reg.item())
+        out[pre + "triplets"] = trip.numpy().astype(np.int16)
+        out[pre + "loss"], out[pre + "bpr"], out[pre + "reg"] = (np.float64(v.item()) for v in (loss, bpr, reg))
+        no_grad = []
+        for name, prm in params:
+            if prm.grad is None:
+                no_grad.append(name)
+            else:
+                out[pre + "grad." + name] = R.rows(_flat2(prm.grad.numpy()), S["grad"]).copy()
+        assert tuple(no_grad) == R.UNUSED, no_grad
+        trainer.optimizer.step()
+        for name, prm in params:
+            out[pre + "param." + name] = R.rows(_flat2(prm.detach().numpy()), S["param"]).copy()
+    out["no_grad"] = np.array(no_grad)
+    out["row_strides"] = np.array([f"{k}={v}" for k, v in S.items()])
+    out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()] +
+                              [f"{k}={config[k]}" for k in ("embedding_size", "n_layers")])
+    path = os.path.join(out_dir, "dualgnn_step0_small.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}: {os.path.getsize(path) / 1e6:.2f} MB, keys={len(out)}")
+
+    # ---- pass 2: two epochs through the reference's Trainer
+    config, hp, train, valid, test, model, trainer = _dualgnn_model()
+    params = fixed(model)
+    for n, p in params:
+        assert np.array_equal(p.detach().numpy(), init[n]), n
+    assert np.array_equal(model.result_embed.numpy(), result0)
+    out = {"n_users": np.int64(nu), "n_items": np.int64(ni)}
+    out["train_u"], out["train_i"] = train_u.astype(np.int16), train_i.astype(np.int16)
+    lens = np.array([len(lists[u][0]) for u in range(nu)], dtype=np.int64)
+    out["ug_ptr"] = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    out["ug_nbr"] = np.concatenate([np.asarray(lists[u][0], dtype=np.int16) for u in range(nu)])
+    cnt = np.concatenate([np.asarray(lists[u][1], dtype=np.float64) for u in range(nu)])
+    assert cnt.max() <= 255 and np.array_equal(cnt, np.round(cnt))
+    out["ug_cnt"] = cnt.astype(np.uint8)
+    for n, v in init.items():
+        out["init." + n] = R.rows(_flat2(v), S["param"]).copy()
+    out["const.result_embed"] = result0.astype(np.float32)[::S["const"]].copy()
+    out["v_feat"], out["t_feat"] = model.v_feat.numpy().copy(), model.t_feat.numpy().copy()
+    rec = _Recorder(train)
+    _eval_dump(trainer, model, valid, "init_valid", out)
+    losses = []
+    for epoch in range(2):
+        model.pre_epoch_processing()
+        out[f"epoch{epoch}_idx"] = np.asarray(model.epoch_user_graph, dtype=np.int16)
+        out[f"epoch{epoch}_W"] = model.user_weight_matrix.numpy().copy()
+        if epoch == 0:
+            assert np.array_equal(out["epoch0_idx"], idx0) and np.array_equal(out["epoch0_W"], W0)
+        n0 = len(rec.batches)
+        loss_sum, _ = trainer._train_epoch(train, epoch)
+        trainer.lr_scheduler.step()
+        losses.append(float(loss_sum))
+        out[f"epoch{epoch}_nbatch"] = np.int64(len(rec.batches) - n0)
+        for name, prm in params:
+            out[f"epoch{epoch}_param." + name] = R.rows(_flat2(prm.detach().numpy()),
+                                                         S["last" if epoch == 1 else "epoch"]).copy()
+    out["epoch_losses"] = np.array(losses)
+    _eval_dump(trainer, model, valid, "epoch1_valid", out)
+    _eval_dump(trainer, model, test, "epoch1_test", out)
+    for tag, ld in (("valid", valid), ("test", test)):
+        out[f"{tag}_eval_u"] = ld.get_eval_users().numpy().astype(np.int64)
+        out[f"{tag}_eval_len"] = np.asarray(ld.get_eval_len_list(), dtype=np.int64)
+        out[f"{tag}_eval_items"] = np.concatenate([np.asarray(x, dtype=np.int64) for x in ld.get_eval_items()])
+    out["row_strides"] = np.array([f"{k}={v}" for k, v in S.items()])
+    out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()])
+    path = os.path.join(out_dir, "dualgnn_small.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}: {os.path.getsize(path) / 1e6:.2f} MB, keys={len(out)}")
+    for f in ("dualgnn_small.npz", "dualgnn_step0_small.npz"):
+        assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn")
+    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn | dualgnn")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     _install_shims()
@@ -1490,6 +1730,9 @@ def main():
         return
     if args.only == "mmgcn":
         capture_mmgcn(args.out)
+        return
+    if args.only == "dualgnn":
+        capture_dualgnn(args.out)
         return
     if args.only == "mf":
         capture_mf(args.out)

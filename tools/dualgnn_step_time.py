@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""ms/step of the DualGNN training step at a baby-like synthetic shape (19,445 users, 7,050 items,
+raw features 4096 / 384 wide, d = 64, B = 2048) on rsx.synth data, the user graph from
+rsx.dualgnn.build_user_graph on the synthetic interactions.
+
+Measured, each as `--repeats` windows of `--steps` iterations between two device events after
+a warm-up on the timed shape (median, and minimum / maximum as the spread):
+  * the step (zero_grad, forward, loss, backward, RsxAdam) replayed from the Trainer's captured
+    graph and launched eagerly;
+  * each stage of a step on the step's own tensors, forward and backward, and its share of the
+    eager forward + backward: the two MLPs with the normalisation, the propagation x + A x + A^2 x
+    of both modalities, and the tail (mix, user graph, loss and their backwards);
+  * the same forward, loss and backward composed from torch ops as the reference writes them
+    (tests/dualgnn_ref.py in float32 on the GPU, the operator a torch sparse tensor), alternated
+    window by window with the HIP path;
+  * rsx_dualgnn_ugraph_fwd against the same lists as a CSR through rsx_spmm with the ADD
+    epilogue, alternated window by window; and the backward's SpMM on the transposed lists.
+Prints one JSON line.  Needs a GPU: there is no CPU fallback for the measured path.
+
+Usage:  python tools/dualgnn_step_time.py [--steps 20] [--repeats 5] [--warmup 5] [--scale 1.0]
+"""
+from __future__ import annotations
+
+import json
+
+import numpy as np
+import torch
+
+from _step_time import alternated, parser, require_gpu, synth_model, trainer_runs
+
+
+def main():
+    args = parser(steps=20, warmup=5).parse_args()
+    require_gpu("dualgnn_step_time", args)
+    import dualgnn_ref as R
+    from rsx import _lib as L
+    from rsx import dualgnn as M
+    from rsx import ops
+    from rsx.grcn import _Mlp
+    from rsx.mmgcn import _Gemm, _Normalize
+    from rsx.optim import RsxAdam
+
+    m, c, batches, n_edges = synth_model("DualGNN", "baby", args, dict(learning_rate=0.001, reg_weight=0.001,
+                                                                        is_multimodal_model=True),
+                                         (("image_feat_raw.npy", 4096, 5), ("text_feat_raw.npy", 384, 6)))
+    m.train()
+    np.random.seed(999)
+    m.pre_epoch_processing()
+    d, B, nu, ni, n = m.dim_latent, 2048, m.n_users, m.n_items, m.n_nodes
+    dev = m.device
+    lens = np.diff(m.user_graph.ptr)
+    res = {"n_users": nu, "n_items": ni, "train_edges": n_edges, "d": d, "F": [4096, 384], "batch": B, "k": m.k,
+           "user_lists": {"source": m.user_graph_source, "shorter_than_k": int((lens < m.k).sum()), "empty": int((lens == 0).sum())},
+           "transposed_lists": {"n_long": int(m.PT.n_long), "max_in_degree": int(np.diff(m.PT.rowptr_host).max())},
+           "steps_per_window": args.steps, "windows": args.repeats, "warmup": args.warmup, "format": "[median, min, max] ms"}
+    trip = batches[0]
+    one = torch.ones((), device=dev)
+
+    def leaf(x):
+        x = x.detach().requires_grad_(True)
+        x.grad = None
+        return x
+
+    def fwd_bwd(make):
+        def run():
+            m.zero_grad(set_to_none=True)
+            make().backward(one)
+        return run
+
+    mods = m._mods()
+    with torch.no_grad():
+        xn = {k: _Normalize.apply(torch.cat([g.preference, _Gemm.apply(_Mlp.apply(f, g.MLP.weight, g.MLP.bias), None,
+                                                                         g.MLP_1.weight, g.MLP_1.bias, False, False)]))
+              for k, g, f in mods}
+        xh = {k: M.propagate(m.A, x) for k, x in xn.items()}
+
+    def mlp():
+        out = 0
+        for k, g, f in mods:
+            temp = _Gemm.apply(_Mlp.apply(f, g.MLP.weight, g.MLP.bias), None, g.MLP_1.weight, g.MLP_1.bias, False, False)
+            out = out + _Normalize.apply(torch.cat([g.preference, temp], dim=0)).sum()
+        return out
+
+    def prop():
+        return sum(M._Prop.apply(leaf(xn[k]), m.A).sum() for k, _, _ in mods)
+
+    def tail():
+        cfg = (nu, m.reg_weight, m.result, m.epoch_idx, m.epoch_W, m.PT, m._ws, None)
+        return M._Tail.apply(cfg, trip, leaf(xh["v"]), leaf(xh["t"]), m.weight_u, m.weight_i, m.v_gcn.preference,
+                             m.t_gcn.preference)
+
+    def whole():
+        return m.calculate_loss(trip)
+
+    opt = RsxAdam([p for name, p in m.named_parameters() if name not in R.UNUSED], lr=1e-3)
+    fwd_bwd(whole)()  # gradients for the update to read
+
+    # the reference's ops in float32 torch on the same tensors
+    P = {name: p for name, p in m.named_parameters()}
+    rows = torch.repeat_interleave(torch.arange(n, device=dev), m.A.rowptr[1:] - m.A.rowptr[:-1])
+    A = torch.sparse_coo_tensor(torch.stack([rows, m.A.col.long()]), m.A.val, (n, n)).coalesce()
+    feats = {"v": m.v_feat, "t": m.t_feat}
+    idx64 = m.epoch_idx.long()
+
+    def torch_whole():
+        result, _, _ = R.forward(P, feats, A, idx64, m.epoch_W, nu)
+        return R.loss(P, feats, result, trip, nu, m.reg_weight)[0]
+
+    with torch.no_grad():
+        res["hip_vs_torch_loss_rel_diff"] = float(abs(whole() - torch_whole()) / abs(torch_whole()))
+    res.update(alternated(args, {"model_fwd_bwd_eager": fwd_bwd(whole), "model_fwd_bwd_torch_ops": fwd_bwd(torch_whole)}))
+    res.update(alternated(args, {"mlp_fwd_bwd": fwd_bwd(mlp), "prop_fwd_bwd": fwd_bwd(prop), "tail_fwd_bwd": fwd_bwd(tail)}))
+    fwd_bwd(whole)()
+    res.update(alternated(args, {"adam": opt.step}))
+    total = res["model_fwd_bwd_eager"][0]
+    res["share_of_fwd_bwd"] = {k: round(res[k + "_fwd_bwd"][0] / total, 3) for k in ("mlp", "prop", "tail")}
+    m.zero_grad(set_to_none=True)
+
+    # ---- the user graph's forward: the ELL kernel against the same lists as a CSR on the SpMM
+    user_rep = m.last_user_rep
+    idx, W = m.epoch_idx.cpu().numpy(), m.epoch_W.cpu().numpy()
+    Pcsr = ops.DeviceCSR(np.arange(nu + 1, dtype=np.int64) * m.k, idx.reshape(-1), W.reshape(-1), nu, dev, m.chunk)
+    out_a, out_b = torch.empty_like(user_rep), torch.empty_like(user_rep)
+    g = torch.randn(n, d, device=dev)
+    res.update(alternated(args, {
+        "ugraph_fwd_kernel": lambda: M.ugraph_fwd(user_rep, m.epoch_idx, m.epoch_W, out=out_a),
+        "ugraph_fwd_spmm_add": lambda: Pcsr.spmm_epi(user_rep, ops.epi(L.RSX_EPI_ADD, y=out_b, s_in=user_rep), d),
+        "ugraph_bwd_spmm_add": lambda: M.ugraph_bwd(m.PT, g, nu)}, steps=5 * args.steps))
+    res["ugraph_kernel_vs_spmm_max_abs_diff"] = float((out_a - out_b).abs().max())
+
+    # ---- the step through the Trainer, eager and captured
+    res.update(trainer_runs(args, c, m, batches))
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
