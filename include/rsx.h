@@ -1644,7 +1644,7 @@ int rsx_lgm_loss_bwd(const rsx_lgm_loss_args* a, const float* go, float* gC, flo
                      float* gGt, void* ws, size_t ws_bytes, rsx_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
-/* MMGCN: modal-GCN layers, the wide product, normalise, loss (mmgcn.hip)     */
+/* MMGCN: the fused modal-GCN layer and the loss (mmgcn.hip)                  */
 /* ------------------------------------------------------------------------ */
 /*
  * One modal-GCN layer of width d (reference src/models/mmgcn.py:176-186, the concatenating
@@ -1667,48 +1667,6 @@ int rsx_mmgcn_layer_fwd(const float* a, const float* x, const float* E, const fl
 int rsx_mmgcn_layer_bwd(const float* g_out, const float* out, const float* h, const float* u, const float* E,
                         const float* Wc, const float* Wl, const float* Wg, int64_t n, int32_t d, float* go, float* gh,
                         float* gu, float* xh, float* g_a, float* g_x, rsx_stream_t stream);
-/*
- * The wide product of layer 1 and of the image MLP, and its data gradient:
- *   P = (X .* slope(mx)) op(B) + bias        X = [x0 (k0 columns, row stride ld0) | x1 (k1, ld1)]
- *   V = act ? leaky(P) : P;  V = V .* slope(my);  y = V;  y2 = V + r
- * slope(t) = 1 where t > 0, else 0.01 (t a saved leaky output).  mx [n, k0] (row stride ldmx;
- * needs k1 = 0), xm_out [n, k0] receives the masked X (a weight gradient's rows), my, r, y, y2
- * [n, n_out] contiguous; any of mx, xm_out, bias, my, r and one of y, y2 may be NULL (y2 without
- * r is V).  B is [K, n_out] (b_kn = 1) or [n_out, K] (b_kn = 0), K = k0 + k1, row stride ldb:
- * a column block of a wider weight is given by its first element and the weight's stride.
- * The data gradient of Y = leaky(X W^T + b) is the same call with x0 = dY, mx = Y, B = W and
- * b_kn = 1.  n_out a multiple of 32; k0, k1 and the strides multiples of 4 (a ragged last
- * 32-wide slab is masked); every pointer 16-byte aligned; else RSX_ERR_UNSUPPORTED / _ARG.
- * f32 MFMA, one fixed summation order: deterministic.
- */
-typedef struct rsx_mmgcn_gemm_args {
-    const float* x0;
-    const float* x1;
-    const float* mx;
-    float* xm_out;
-    const float* B;
-    const float* bias;
-    const float* my;
-    const float* r;
-    float* y;
-    float* y2;
-    int64_t n, ld0, ld1, ldmx, ldb;
-    int32_t k0, k1, n_out, b_kn, act, pad0;
-} rsx_mmgcn_gemm_args;
-int rsx_mmgcn_gemm(const rsx_mmgcn_gemm_args* a, rsx_stream_t stream);
-/*
- * F.normalize over the rows of x [n, w] (mmgcn.py:168): y = x / max(|x|_2, 1e-12), den[row] the
- * divisor (y may be x); and torch's backward from y and den: (g - y <g, y>) / den, or g / den on a
- * row whose norm was clamped (no gradient passes through the clamp).  w a multiple of 4.
- */
-int rsx_mmgcn_normalize_fwd(const float* x, int64_t n, int32_t w, float* y, float* den, rsx_stream_t stream);
-int rsx_mmgcn_normalize_bwd(const float* gy, const float* y, const float* den, int64_t n, int32_t w, float* gx,
-                            rsx_stream_t stream);
-/* out[n_cols] = the column sums of g [n, n_cols] (a bias gradient): partial sums over blocks of
- * 128 rows, added in block order (deterministic). */
-size_t rsx_mmgcn_colsum_ws_bytes(int64_t n, int32_t n_cols);
-int rsx_mmgcn_colsum(const float* g, int64_t n, int32_t n_cols, float* out, void* ws, size_t ws_bytes,
-                     rsx_stream_t stream);
 /*
  * MMGCN's loss (mmgcn.py:79-97) on the modality tables xv, xt [n_users + n_items, d] (either
  * may be NULL: num_modal = the number given) and the constant id table E.  With
@@ -1734,6 +1692,57 @@ int rsx_mmgcn_loss_fwd(const rsx_mmgcn_loss_args* a, float* out, float* result, 
                        rsx_stream_t stream);
 int rsx_mmgcn_loss_bwd(const rsx_mmgcn_loss_args* a, const float* go, float* g, void* ws, size_t ws_bytes,
                        rsx_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* Dense layer blocks the models share: the wide product, normalise, the      */
+/* column sum, the leaky mask (dense.hip)                                     */
+/* ------------------------------------------------------------------------ */
+/*
+ * The wide product (MMGCN's layer 1 and image MLP, GRCN's and DualGNN's content MLPs) and its
+ * data gradient:
+ *   P = (X .* slope(mx)) op(B) + bias        X = [x0 (k0 columns, row stride ld0) | x1 (k1, ld1)]
+ *   V = act ? leaky(P) : P;  V = V .* slope(my);  y = V;  y2 = V + r
+ * slope(t) = 1 where t > 0, else 0.01 (t a saved leaky output).  mx [n, k0] (row stride ldmx;
+ * needs k1 = 0), xm_out [n, k0] receives the masked X (a weight gradient's rows), my, r, y, y2
+ * [n, n_out] contiguous; any of mx, xm_out, bias, my, r and one of y, y2 may be NULL (y2 without
+ * r is V).  B is [K, n_out] (b_kn = 1) or [n_out, K] (b_kn = 0), K = k0 + k1, row stride ldb:
+ * a column block of a wider weight is given by its first element and the weight's stride.
+ * The data gradient of Y = leaky(X W^T + b) is the same call with x0 = dY, mx = Y, B = W and
+ * b_kn = 1.  n_out a multiple of 32; k0, k1 and the strides multiples of 4 (a ragged last
+ * 32-wide slab is masked); every pointer 16-byte aligned; else RSX_ERR_UNSUPPORTED / _ARG.
+ * f32 MFMA, one fixed summation order: deterministic.
+ */
+typedef struct rsx_dense_gemm_args {
+    const float* x0;
+    const float* x1;
+    const float* mx;
+    float* xm_out;
+    const float* B;
+    const float* bias;
+    const float* my;
+    const float* r;
+    float* y;
+    float* y2;
+    int64_t n, ld0, ld1, ldmx, ldb;
+    int32_t k0, k1, n_out, b_kn, act, pad0;
+} rsx_dense_gemm_args;
+int rsx_dense_gemm(const rsx_dense_gemm_args* a, rsx_stream_t stream);
+/*
+ * F.normalize over the rows of x [n, w] (mmgcn.py:168): y = x / max(|x|_2, 1e-12), den[row] the
+ * divisor (y may be x); and torch's backward from y and den: (g - y <g, y>) / den, or g / den on a
+ * row whose norm was clamped (no gradient passes through the clamp).  w a multiple of 4.
+ */
+int rsx_dense_normalize_fwd(const float* x, int64_t n, int32_t w, float* y, float* den, rsx_stream_t stream);
+int rsx_dense_normalize_bwd(const float* gy, const float* y, const float* den, int64_t n, int32_t w, float* gx,
+                            rsx_stream_t stream);
+/* out[n_cols] = the column sums of g [n, n_cols] (a bias gradient): partial sums over blocks of
+ * 128 rows, added in block order (deterministic). */
+size_t rsx_dense_colsum_ws_bytes(int64_t n, int32_t n_cols);
+int rsx_dense_colsum(const float* g, int64_t n, int32_t n_cols, float* out, void* ws, size_t ws_bytes,
+                     rsx_stream_t stream);
+/* out = g .* slope(y) over n_elems floats (a multiple of 4), y a saved leaky_relu output: slope
+ * 1 where y > 0, else 0.01 (the backward of leaky(X W^T + b) when no data gradient is wanted). */
+int rsx_dense_leaky_bwd(const float* g, const float* y, int64_t n_elems, float* out, rsx_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* GRCN: edge attention, the refined edge weight, SDDMM, loss (grcn.hip)      */
@@ -1793,9 +1802,6 @@ int rsx_grcn_edge_dots(const float* G, const float* h1, const float* D, const fl
 int rsx_grcn_refine_bwd(int32_t n_mod, const float* alpha0, const float* alpha1, const float* conf, const float* dw,
                         const int64_t* rowptr, const int32_t* rev, int64_t n, int64_t nnz, float* dalpha0,
                         float* dalpha1, float* dconf, rsx_stream_t stream);
-/* out = g .* slope(y) over n_elems floats (a multiple of 4), y a saved leaky_relu output: slope
- * 1 where y > 0, else 0.01 (the content MLP's backward, grcn.py:141). */
-int rsx_grcn_leaky_bwd(const float* g, const float* y, int64_t n_elems, float* out, rsx_stream_t stream);
 /*
  * GRCN's loss (grcn.py:300-333) on the representation [id_rep | rep_v | rep_t] given as its
  * tables, not concatenated: id_rep [n, dx], rep_v and rep_t [n, dc] (rep_t and pref_t NULL

@@ -298,16 +298,6 @@ __global__ __launch_bounds__(256) void refine_fwd(Graph gr, int M, const float* 
     if (in_range(re, gr.nnz)) valT[re] = w;
 }
 
-// out = g .* slope(y), y a saved leaky_relu output (slope 0.01 where y <= 0): the MLP's backward
-__global__ __launch_bounds__(256) void leaky_bwd(const float* __restrict__ g, const float* __restrict__ y, int64_t n4,
-                                                 float* __restrict__ out) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-        const float4 gv = ld4(g + 4 * i), yv = ld4(y + 4 * i);
-        st4(out + 4 * i, make_float4(yv.x > 0.f ? gv.x : 0.01f * gv.x, yv.y > 0.f ? gv.y : 0.01f * gv.y,
-                                     yv.z > 0.f ? gv.z : 0.01f * gv.z, yv.w > 0.f ? gv.w : 0.01f * gv.w));
-    }
-}
-
 // dw_e = <G_t, h1_s> + <D_t, x_s>, t = row(e) = col[rev[e]], s = col[e]: a lane group an edge
 template <int D>
 __global__ __launch_bounds__(256) void edge_dots(Graph gr, const float* __restrict__ G, const float* __restrict__ h1,
@@ -676,15 +666,6 @@ int rsx_grcn_refine_bwd(int32_t n_mod, const float* alpha0, const float* alpha1,
     const grcn::Graph g{rowptr, nullptr, rev, n, nnz};
     hipLaunchKernelGGL(grcn::refine_bwd, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, as_stream(stream), g, (int)n_mod,
                        alpha0, alpha1, conf, dw, dalpha0, dalpha1, dconf);
-    return last_rc();
-}
-
-int rsx_grcn_leaky_bwd(const float* g, const float* y, int64_t n_elems, float* out, rsx_stream_t stream) {
-    if (n_elems < 0 || !g || !y || !out || !aligned16(g) || !aligned16(y) || !aligned16(out)) return RSX_ERR_ARG;
-    if (n_elems % 4) return RSX_ERR_UNSUPPORTED;
-    if (n_elems == 0) return RSX_OK;
-    hipLaunchKernelGGL(grcn::leaky_bwd, dim3(grcn::capped((n_elems / 4 + 255) / 256, 4096)), dim3(256), 0,
-                       as_stream(stream), g, y, n_elems / 4, out);
     return last_rc();
 }
 

@@ -3,7 +3,8 @@
 // wave as the transposed accumulator layout of v_mfma_f32_16x16x4f32 (lane
 // l = n + 16 g holds row n, features 16 t + 4 g + r in register 4 t + r; see the
 // header of smore_fuse.hip), Linear products on it, LDS weight staging, the
-// activations and the dropout mask.
+// activations (leaky_relu and its slope mask for mmgcn.hip and dense.hip among
+// them) and the dropout mask.
 #pragma once
 #include <cmath>
 
@@ -260,6 +261,21 @@ struct Tanh {
 };
 constexpr Sigm sigm{};
 constexpr Tanh tanh_{};
+
+constexpr float kSlope = 0.01f;  // F.leaky_relu's default
+
+struct Leaky {
+    __device__ float operator()(float v) const { return v > 0.f ? v : kSlope * v; }
+};
+struct MulSlope {  // g * slope(y): y a saved leaky output
+    __device__ float operator()(float g, float y) const { return y > 0.f ? g : kSlope * g; }
+};
+constexpr Leaky leaky{};
+constexpr MulSlope mul_slope{};
+
+__device__ __forceinline__ float4 mul_slope4(float4 g, float4 y) {
+    return make_float4(mul_slope(g.x, y.x), mul_slope(g.y, y.y), mul_slope(g.z, y.z), mul_slope(g.w, y.w));
+}
 
 template <int D>
 __device__ __forceinline__ Fld<D> softmax_row(const Fld<D>& q) {

@@ -147,7 +147,7 @@ class LgmLossArgs(C.Structure):
                 ("n_items", I64), ("batch", I64), ("d", I32), ("alpha", F32), ("reg", F32), ("pad0", I32)]
 
 
-class MmgcnGemmArgs(C.Structure):
+class DenseGemmArgs(C.Structure):
     _fields_ = [("x0", P), ("x1", P), ("mx", P), ("xm_out", P), ("B", P), ("bias", P), ("my", P), ("r", P), ("y", P),
                 ("y2", P), ("n", I64), ("ld0", I64), ("ld1", I64), ("ldmx", I64), ("ldb", I64), ("k0", I32),
                 ("k1", I32), ("n_out", I32), ("b_kn", I32), ("act", I32), ("pad0", I32)]
@@ -318,11 +318,12 @@ def _declare(lib):
         "rsx_lgm_loss_bwd": (C.c_int, [C.POINTER(LgmLossArgs), P, P, P, P, P, P, P, C.c_size_t, P]),
         "rsx_mmgcn_layer_fwd": (C.c_int, [P, P, P, P, P, P, P, P, I64, I32, P, P, P, P]),
         "rsx_mmgcn_layer_bwd": (C.c_int, [P, P, P, P, P, P, P, P, I64, I32, P, P, P, P, P, P, P]),
-        "rsx_mmgcn_gemm": (C.c_int, [C.POINTER(MmgcnGemmArgs), P]),
-        "rsx_mmgcn_normalize_fwd": (C.c_int, [P, I64, I32, P, P, P]),
-        "rsx_mmgcn_normalize_bwd": (C.c_int, [P, P, P, I64, I32, P, P]),
-        "rsx_mmgcn_colsum_ws_bytes": (C.c_size_t, [I64, I32]),
-        "rsx_mmgcn_colsum": (C.c_int, [P, I64, I32, P, P, C.c_size_t, P]),
+        "rsx_dense_gemm": (C.c_int, [C.POINTER(DenseGemmArgs), P]),
+        "rsx_dense_normalize_fwd": (C.c_int, [P, I64, I32, P, P, P]),
+        "rsx_dense_normalize_bwd": (C.c_int, [P, P, P, I64, I32, P, P]),
+        "rsx_dense_colsum_ws_bytes": (C.c_size_t, [I64, I32]),
+        "rsx_dense_colsum": (C.c_int, [P, I64, I32, P, P, C.c_size_t, P]),
+        "rsx_dense_leaky_bwd": (C.c_int, [P, P, I64, P, P]),
         "rsx_mmgcn_loss_ws_bytes": (C.c_size_t, [I64, I32]),
         "rsx_mmgcn_loss_fwd": (C.c_int, [C.POINTER(MmgcnLossArgs), P, P, P, C.c_size_t, P]),
         "rsx_mmgcn_loss_bwd": (C.c_int, [C.POINTER(MmgcnLossArgs), P, P, P, C.c_size_t, P]),
@@ -332,7 +333,6 @@ def _declare(lib):
         "rsx_grcn_refine_fwd": (C.c_int, [I32, P, P, P, P, P, I64, I64, P, P, P]),
         "rsx_grcn_edge_dots": (C.c_int, [P, P, P, P, P, P, I64, I64, I32, P, P]),
         "rsx_grcn_refine_bwd": (C.c_int, [I32, P, P, P, P, P, P, I64, I64, P, P, P, P]),
-        "rsx_grcn_leaky_bwd": (C.c_int, [P, P, I64, P, P]),
         "rsx_grcn_loss_ws_bytes": (C.c_size_t, [I64, I32]),
         "rsx_grcn_loss_fwd": (C.c_int, [C.POINTER(GrcnLossArgs), P, P, I64, P, C.c_size_t, P]),
         "rsx_grcn_loss_bwd": (C.c_int, [C.POINTER(GrcnLossArgs), P, P, P, P, P, P, P, P, C.c_size_t, P]),
@@ -386,11 +386,12 @@ EXPORTED = ["rsx_version", "rsx_csr_schedule_host", "rsx_csr_schedule_rebind", "
             "rsx_lgm_ssl_ws_bytes", "rsx_lgm_ssl_fwd", "rsx_lgm_ssl_bwd", "rsx_lgm_assign_fwd", "rsx_lgm_assign_bwd", "rsx_lgm_gumbel_of_bits",
             "rsx_lgm_hgnn_ws_bytes", "rsx_lgm_hgnn_reduce", "rsx_lgm_hgnn_expand", "rsx_lgm_hgnn_rowdots",
             "rsx_lgm_loss_ws_bytes", "rsx_lgm_loss_fwd", "rsx_lgm_loss_bwd",
-            "rsx_mmgcn_layer_fwd", "rsx_mmgcn_layer_bwd", "rsx_mmgcn_gemm", "rsx_mmgcn_normalize_fwd",
-            "rsx_mmgcn_normalize_bwd", "rsx_mmgcn_colsum_ws_bytes", "rsx_mmgcn_colsum", "rsx_mmgcn_loss_ws_bytes",
-            "rsx_mmgcn_loss_fwd", "rsx_mmgcn_loss_bwd",
+            "rsx_dense_gemm", "rsx_dense_normalize_fwd", "rsx_dense_normalize_bwd", "rsx_dense_colsum_ws_bytes",
+            "rsx_dense_colsum", "rsx_dense_leaky_bwd",
+            "rsx_mmgcn_layer_fwd", "rsx_mmgcn_layer_bwd", "rsx_mmgcn_loss_ws_bytes", "rsx_mmgcn_loss_fwd",
+            "rsx_mmgcn_loss_bwd",
             "rsx_grcn_hub_degree", "rsx_grcn_attn_fwd", "rsx_grcn_attn_bwd", "rsx_grcn_refine_fwd", "rsx_grcn_edge_dots",
-            "rsx_grcn_refine_bwd", "rsx_grcn_leaky_bwd", "rsx_grcn_loss_ws_bytes", "rsx_grcn_loss_fwd", "rsx_grcn_loss_bwd",
+            "rsx_grcn_refine_bwd", "rsx_grcn_loss_ws_bytes", "rsx_grcn_loss_fwd", "rsx_grcn_loss_bwd",
             "rsx_dualgnn_mix_fwd", "rsx_dualgnn_mix_bwd", "rsx_dualgnn_ugraph_fwd", "rsx_dualgnn_loss_ws_bytes",
             "rsx_dualgnn_loss_fwd", "rsx_dualgnn_loss_bwd",
             "rsx_cpu_spmm", "rsx_cpu_propagate_mean", "rsx_cpu_layergcn_forward", "rsx_cpu_layergcn_backward",

@@ -2,8 +2,8 @@
 FREEDOM, LATTICE): the mean-of-layers propagation, dense (`_PropMean`) and on the tagged
 batch rows (`_PropMeanRows`, `_RowTags`, `ui_backbone`), the joint [U; I] table (`_join_tables`,
 `_ego`), the per-batch-size index caches (`_RowsOff`, `_BatchIndex`), a sparse operator with
-its transpose (`_DevGraph`), the whole-table projection (`_Project`) and the kNN item graphs
-(`knn_graph`, `knn_graph_device`, `load_reference_knn`, `cached_knn`).
+its transpose (`_DevGraph`) and the kNN item graphs (`knn_graph`, `knn_graph_device`,
+`load_reference_knn`, `cached_knn`).  The dense layer blocks are rsx.dense's.
 
 Models import this module; it imports no model.
 """
@@ -210,23 +210,6 @@ def ui_backbone(model, ego, A, K, rows=None, bw_rows=None, AT=None):
         model._tags.mark(rows)
         return _PropMeanRows.apply(ego, A, K, model._tags, bw_rows if bw_rows is not None else rows, AT)
     return _PropMean.apply(ego, A, K, AT)
-
-
-class _Project(torch.autograd.Function):
-    """x W^T + b over every row of a feature table: rsx_linear_rows_fwd, and rsx_linear_bwd
-    (dX, dW, db in one pass over the rows) for the dense gradient BM3 sends back."""
-
-    @staticmethod
-    def forward(ctx, x, W, b):
-        x, W, b = x.contiguous(), W.contiguous(), b.contiguous()
-        ctx.save_for_backward(x, W)
-        return ops.linear_rows_fwd(x, W, b, None)
-
-    @staticmethod
-    def backward(ctx, g):
-        x, W = ctx.saved_tensors
-        dw, dx, db = ops.linear_bwd(g.contiguous(), x, W, bias=True)
-        return dx, dw, db
 
 
 def knn_graph(feat: np.ndarray, k: int):

@@ -31,7 +31,8 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
-from .blocks import _ego, _join_tables, _Project, _PropMean
+from .blocks import _ego, _join_tables, _PropMean
+from .dense import _Project
 from .recommender import GeneralRecommender
 
 SUPPORTED_D = (32, 64, 128)

@@ -22,7 +22,7 @@ and scoring (:141-205), as the reference really computes them:
 
 The user graph is host work (rsx.dualgnn.load_user_graph / build_user_graph / topk_sample); the
 step's kernels are csrc/dualgnn.hip (rsx_dualgnn_mix_*, rsx_dualgnn_ugraph_fwd,
-rsx_dualgnn_loss_*), the MLP and F.normalize are rsx.mmgcn's wide product and normalise, A x
+rsx_dualgnn_loss_*), the MLP and F.normalize are rsx.dense's wide product and normalise, A x
 and the user graph's backward (the transposed lists as a CSR) run on rsx_spmm.
 
 One GPU; anything the kernels are not built for raises RSX_ERR_UNSUPPORTED at construction.
@@ -41,6 +41,7 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import ops
+from .dense import _Gemm, _Normalize
 from .recommender import GeneralRecommender
 
 DIM_LATENT = 64  # dualgnn.py:47
@@ -495,10 +496,8 @@ class DualGNN(GeneralRecommender):
     # --------------------------------------------------------------- forward
     def _modal(self, g: GCN, feat: torch.Tensor):
         """x_hat [n, 64] of one modality (dualgnn.py:304-315), with autograd."""
-        from .grcn import _Mlp  # leaky(X W^T + b) on a constant X of any width that is a multiple of 4
-        from .mmgcn import _Gemm, _Normalize
-
-        hid = _Mlp.apply(feat, g.MLP.weight, g.MLP.bias)
+        # leaky(X W^T + b) on a constant X of any width that is a multiple of 4
+        hid = _Gemm.apply(feat, None, g.MLP.weight, g.MLP.bias, False, True)
         temp = _Gemm.apply(hid, None, g.MLP_1.weight, g.MLP_1.bias, False, False)
         x = _Normalize.apply(torch.cat([g.preference, temp], dim=0))
         return _Prop.apply(x, self.A)

@@ -13,7 +13,7 @@ weights), forward, loss and scoring (:166-222):
   normalised, mixed by mm_image_weight (`freedom_item_graph`: construction-time host work;
   the neighbour ids from rsx_knn_graph or a CPU top-k);
 * the UI backbone on the batch rows (`rsx.blocks.ui_backbone`), the item graph's propagation
-  (`_DevGraph`), the whole-table feature projections (`rsx.blocks._Project`);
+  (`_DevGraph`), the whole-table feature projections (`rsx.dense._Project`);
 * the three-term BPR loss, forward and backward: rsx_freedom_loss_fwd / _bwd
   (csrc/freedom.hip), deterministic;
 * evaluation: the fused full-sort on the cached eval-mode tables.
@@ -32,8 +32,9 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import graph, ops
-from .blocks import (_DevGraph, _ego, _join_tables, _Project, _PropMean, _RowsOff, knn_graph_device,
+from .blocks import (_DevGraph, _ego, _join_tables, _PropMean, _RowsOff, knn_graph_device,
                      load_reference_knn, ui_backbone)
+from .dense import _Project
 from .layergcn import DeviceEdgeDropout
 from .recommender import EvalTables, GeneralRecommender
 

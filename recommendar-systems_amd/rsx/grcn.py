@@ -20,8 +20,8 @@ buffers that rsx_grcn_refine_fwd rewrites every step, and both id-GCN products a
 transposes run on rsx_spmm.
 
 Kernels (csrc/grcn.hip): rsx_grcn_attn_fwd / _bwd, rsx_grcn_refine_fwd / _bwd, rsx_grcn_edge_dots,
-rsx_grcn_loss_*, rsx_grcn_leaky_bwd; leaky_relu(X W^T + b) on rsx.mmgcn's wide product (`_Mlp`),
-F.normalize on its `_Normalize`.
+rsx_grcn_loss_*; leaky_relu(X W^T + b) on the shared dense blocks' wide product (rsx.dense._Gemm,
+a constant X: the masked rows from rsx_dense_leaky_bwd), F.normalize on its `_Normalize`.
 
 The step's autograd: ONE Function (`_Step`) from the normalised inputs to the loss word, one
 differentiable output, every tensor kept with save_for_backward (nothing with a grad_fn on ctx: a
@@ -41,6 +41,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from . import ops
+from .dense import _Gemm, _Normalize
 from .recommender import GeneralRecommender
 
 SUPPORTED_D = (64, 128)
@@ -280,33 +281,6 @@ def loss_bwd(a, go, like_id, like_v, like_t, like_pv, ws):
     return g_id, g_v, g_t, gE, gpv, gpt
 
 
-class _Mlp(torch.autograd.Function):
-    """leaky_relu(X W^T + b) for a constant X [n, F] (grcn.py:141): the wide product of rsx.mmgcn, its
-    weight gradient on rsx_linear_wgrad, the bias gradient on rsx_mmgcn_colsum.  (rsx.mmgcn._Gemm
-    with act=True forms the masked rows in a data-gradient launch of n_out = F columns, which
-    takes multiples of 32 only; a feature table is any multiple of 4 wide.)"""
-
-    @staticmethod
-    def forward(ctx, X, W, b):
-        from .mmgcn import gemm
-
-        X, W = X.contiguous(), W.contiguous()
-        y = gemm(X, W, W.shape[0], False, bias=b.contiguous(), act=True)
-        ctx.save_for_backward(X, y)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        from .mmgcn import colsum
-
-        X, y = ctx.saved_tensors
-        g = g.contiguous()
-        gz = torch.empty_like(g)
-        L.check(L.lib().rsx_grcn_leaky_bwd(ops._p(g), ops._p(y), g.numel(), ops._p(gz), ops._stream()),
-                "rsx_grcn_leaky_bwd")
-        return None, ops.linear_wgrad(gz, X), colsum(gz)
-
-
 def step_forward(g: EdgeGraph, xs, conf, xn):
     """The forward between the normalised inputs and the representation tables: (reps, h1, id_rep);
     the alphas and the edge weights land in g's persistent buffers."""
@@ -449,14 +423,12 @@ class GRCN(GeneralRecommender):
     # --------------------------------------------------------------- forward
     def _inputs(self):
         """(x_v, x_t | None, normalize(E)) with autograd: x = [normalize(pref); normalize(leaky(MLP(feat)))]."""
-        from .mmgcn import _Normalize
-
         xs = []
         for g, feat in ((self.v_gcn, self.v_feat), (getattr(self, "t_gcn", None), self.t_feat)):
             if g is None:
                 xs.append(None)
                 continue
-            f = _Normalize.apply(_Mlp.apply(feat, g.MLP.weight, g.MLP.bias))
+            f = _Normalize.apply(_Gemm.apply(feat, None, g.MLP.weight, g.MLP.bias, False, True))
             xs.append(torch.cat([_Normalize.apply(g.preference), f], dim=0))
         return xs[0], xs[1], _Normalize.apply(self.id_gcn.id_embedding)
 

@@ -40,7 +40,8 @@ import torch.nn.functional as F
 
 from . import _lib as L
 from . import graph, ops
-from .blocks import _ego, _join_tables, _Project, _RowsOff, ui_backbone
+from .blocks import _ego, _join_tables, _RowsOff, ui_backbone
+from .dense import _Project
 from .recommender import EvalTables, GeneralRecommender
 
 SUPPORTED_D = (64, 128)

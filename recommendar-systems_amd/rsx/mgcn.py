@@ -30,7 +30,8 @@ from . import _lib as L
 from . import mgcn_fuse as MF
 from . import ops
 from . import smore_fuse as SF
-from .blocks import _BatchIndex, _DevGraph, _ego, _join_tables, _Project, _RowsOff, cached_knn, ui_backbone
+from .blocks import _BatchIndex, _DevGraph, _ego, _join_tables, _RowsOff, cached_knn, ui_backbone
+from .dense import _Project
 from .lightgcn import _BprLoss
 from .nn import RsxLinear
 from .recommender import EvalTables, GeneralRecommender

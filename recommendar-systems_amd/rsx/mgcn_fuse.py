@@ -15,9 +15,10 @@ import torch
 
 from . import _lib as L
 from . import ops
-from .smore_fuse import _arr, _c, _wgrad, supported  # noqa: F401 - `supported` is this module's too
+from .dense import _wgrad
+from .smore_fuse import _c, supported  # noqa: F401 - `supported` is this module's too
 
-_p = ops._p
+_p, _arr = ops._p, ops._arr
 
 
 class _Purify(torch.autograd.Function):

@@ -16,11 +16,12 @@ scoring (:64-105, :164-188), as the reference really computes them:
 * `full_sort_predict` scores `result`, the representation of the last training forward (one
   optimiser step stale; before any training the random table of :56).
 
-Kernels (csrc/mmgcn.hip): layer 1 (width 256 / the text width) and the image MLP on the wide
-product rsx_mmgcn_gemm, its weight gradients on rsx_linear_wgrad, bias gradients on
-rsx_mmgcn_colsum; layers 2 and 3 on the fused rsx_mmgcn_layer_fwd / _bwd with rsx_smore_wgrad;
-F.normalize on rsx_mmgcn_normalize_*; the loss, its dense gradient and `result` on
-rsx_mmgcn_loss_*; A_hat x and A_hat^T g on the SpMM (rsx.blocks._DevGraph).
+Kernels: layer 1 (width 256 / the text width) and the image MLP on the shared dense blocks
+(rsx.dense, csrc/dense.hip): the wide product rsx_dense_gemm, its weight gradients on
+rsx_linear_wgrad, bias gradients on rsx_dense_colsum, F.normalize on rsx_dense_normalize_*;
+layers 2 and 3 on the fused rsx_mmgcn_layer_fwd / _bwd with rsx_smore_wgrad, the loss, its dense
+gradient and `result` on rsx_mmgcn_loss_* (csrc/mmgcn.hip); A_hat x and A_hat^T g on the SpMM
+(rsx.blocks._DevGraph).
 
 One GPU; anything the kernels are not built for raises RSX_ERR_UNSUPPORTED at construction.
 """
@@ -36,8 +37,8 @@ import torch.nn as nn
 from . import _lib as L
 from . import ops
 from .blocks import _DevGraph
+from .dense import _Gemm, _wgrad, colsum, gemm, normalize_bwd, normalize_fwd
 from .recommender import GeneralRecommender
-from .smore_fuse import _wgrad
 
 SUPPORTED_D = (64, 128)
 LATENT = 256  # the image branch's MLP width (mmgcn.py:47)
@@ -122,151 +123,8 @@ def mean_operator(train_u, train_i, n_users: int, n_items: int):
 # ---------------------------------------------------------------------------
 # kernel wrappers
 # ---------------------------------------------------------------------------
-# Every Function below keeps its tensors with save_for_backward, its own outputs included: an
-# output held on ctx directly is a cycle ctx -> output -> grad_fn -> ctx that nothing frees, so
-# an eager batch's autograd graph (its AccumulateGrad nodes bound to the eager stream) would
-# survive into the next batch's HIP-graph capture, whose backward then syncs with a stream
-# outside the capture (rsx.trainer.Trainer.train_step).
-def _col_block(t: torch.Tensor, col0: int) -> int:
-    return t.data_ptr() + 4 * int(col0)
-
-
-def gemm(x0, B, n_out: int, b_kn: bool, *, k0=None, x1=None, mx=None, xm_out=None, bias=None, act=False, my=None,
-         r=None, y=True, b_col0: int = 0):
-    """rsx_mmgcn_gemm on contiguous f32 tensors: V = act((x0[:, :k0] .* slope(mx) | x1) op(B) + bias)
-    .* slope(my).  B: the weight (b_kn: [K, n_out], else [n_out, K]); b_col0 selects the column
-    block [b_col0, b_col0 + width) of a wider weight.  Returns y (V), or y2 = V + r when r is
-    given, or both (y, y2) when r is given and y is True."""
-    ops._gpu(x0, x1, mx, xm_out, B, bias, my, r)
-    n = x0.shape[0]
-    a = L.MmgcnGemmArgs()
-    a.n, a.n_out, a.b_kn, a.act = n, int(n_out), int(b_kn), int(act)
-    a.k0 = int(x0.shape[1] if k0 is None else k0)
-    a.x0, a.ld0 = x0.data_ptr(), x0.shape[1]
-    a.k1 = 0
-    if x1 is not None:
-        a.x1, a.ld1, a.k1 = x1.data_ptr(), x1.shape[1], x1.shape[1]
-    K = a.k0 + a.k1
-    if mx is not None:
-        a.mx, a.ldmx = mx.data_ptr(), mx.shape[1]
-    rows_b, cols_b = (K, n_out) if b_kn else (n_out, K)
-    if B.shape[0] != rows_b or B.shape[1] < b_col0 + cols_b:
-        raise RuntimeError(f"mmgcn gemm: weight {tuple(B.shape)} does not hold a [{rows_b}, {cols_b}] block at column {b_col0}")
-    a.B, a.ldb = _col_block(B, b_col0), B.shape[1]
-    for name, t, shape in (("xm_out", xm_out, (n, a.k0)), ("my", my, (n, n_out)), ("r", r, (n, n_out))):
-        if t is not None:
-            if tuple(t.shape) != shape:
-                raise RuntimeError(f"mmgcn gemm: {name} {tuple(t.shape)}, expected {shape}")
-            setattr(a, name, t.data_ptr())
-    if mx is not None and (mx.shape[0] != n or mx.shape[1] < a.k0):
-        raise RuntimeError("mmgcn gemm: mx does not cover x0")
-    if bias is not None:
-        if bias.numel() != n_out:
-            raise RuntimeError("mmgcn gemm: bias length")
-        a.bias = bias.data_ptr()
-    out = []
-    if y or r is None:
-        yt = torch.empty(n, n_out, dtype=torch.float32, device=x0.device)
-        a.y = yt.data_ptr()
-        out.append(yt)
-    if r is not None:
-        y2 = torch.empty(n, n_out, dtype=torch.float32, device=x0.device)
-        a.y2 = y2.data_ptr()
-        out.append(y2)
-    L.check(L.lib().rsx_mmgcn_gemm(C.byref(a), ops._stream()), "rsx_mmgcn_gemm")
-    return out[0] if len(out) == 1 else tuple(out)
-
-
-def colsum(g: torch.Tensor) -> torch.Tensor:
-    """The column sums of g [n, N] in a fixed order (rsx_mmgcn_colsum)."""
-    ops._gpu(g)
-    n, N = g.shape
-    lib = L.lib()
-    out = torch.empty(N, dtype=torch.float32, device=g.device)
-    ws = torch.empty(max(int(lib.rsx_mmgcn_colsum_ws_bytes(n, N)), 4), dtype=torch.uint8, device=g.device)
-    L.check(lib.rsx_mmgcn_colsum(ops._p(g), n, N, ops._p(out), ops._p(ws), ws.numel(), ops._stream()),
-            "rsx_mmgcn_colsum")
-    return out
-
-
-def normalize_fwd(x: torch.Tensor, out: torch.Tensor | None = None):
-    """(F.normalize(x) over rows, the divisors max(|x|, 1e-12)); `out` may be x."""
-    ops._gpu(x, out)
-    n, w = x.shape
-    y = torch.empty_like(x) if out is None else out
-    den = torch.empty(n, dtype=torch.float32, device=x.device)
-    L.check(L.lib().rsx_mmgcn_normalize_fwd(ops._p(x), n, w, ops._p(y), ops._p(den), ops._stream()),
-            "rsx_mmgcn_normalize_fwd")
-    return y, den
-
-
-def normalize_bwd(gy, y, den):
-    ops._gpu(gy, y, den)
-    n, w = y.shape
-    gx = torch.empty_like(y)
-    L.check(L.lib().rsx_mmgcn_normalize_bwd(ops._p(gy), ops._p(y), ops._p(den), n, w, ops._p(gx), ops._stream()),
-            "rsx_mmgcn_normalize_bwd")
-    return gx
-
-
-class _Normalize(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        y, den = normalize_fwd(x.contiguous())
-        ctx.save_for_backward(y, den)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        return normalize_bwd(g.contiguous(), *ctx.saved_tensors)
-
-
-class _Gemm(torch.autograd.Function):
-    """Y = act(X op(B) + bias) with X the column segments x0 | x1 (x1 may be None): the wide product,
-    its data gradients through the same kernel, its weight gradient through rsx_linear_wgrad."""
-
-    @staticmethod
-    def forward(ctx, x0, x1, B, bias, b_kn, act):
-        x0, B = x0.contiguous(), B.contiguous()
-        x1 = None if x1 is None else x1.contiguous()
-        n_out = B.shape[1] if b_kn else B.shape[0]
-        y = gemm(x0, B, n_out, b_kn, x1=x1, bias=bias, act=act)
-        ctx.b_kn, ctx.act, ctx.has_bias = b_kn, act, bias is not None
-        ctx.save_for_backward(x0, x1, B, y)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        x0, x1, B, y = ctx.saved_tensors
-        g = g.contiguous()
-        k0 = x0.shape[1]
-        go = torch.empty_like(g) if ctx.act else None
-        need = ctx.needs_input_grad
-        gx0 = gx1 = None
-        want1 = x1 is not None and need[1]
-        want0 = need[0] or (ctx.act and not want1)  # the masked rows come out of a data-gradient launch
-        mx = y if ctx.act else None
-        # d X = (g .* slope(y)) op(B)^T: B seen in its other layout, a column block a segment
-        if ctx.b_kn:  # B [K, N]: d X0 = G B[:k0]^T
-            if want0:
-                gx0 = gemm(g, B[:k0], k0, False, mx=mx, xm_out=go)
-            if want1:
-                gx1 = gemm(g, B[k0:], x1.shape[1], False, mx=mx, xm_out=go if gx0 is None else None)
-        else:  # B [N, K]: d X0 = G B[:, :k0]
-            if want0:
-                gx0 = gemm(g, B, k0, True, mx=mx, xm_out=go)
-            if want1:
-                gx1 = gemm(g, B, x1.shape[1], True, mx=mx, xm_out=go if gx0 is None else None, b_col0=k0)
-        gz = go if ctx.act else g
-        gB = gb = None
-        if need[2]:
-            parts = [ops.linear_wgrad(x, gz) if ctx.b_kn else ops.linear_wgrad(gz, x) for x in (x0, x1) if x is not None]
-            gB = parts[0] if len(parts) == 1 else torch.cat(parts, dim=0 if ctx.b_kn else 1)
-        if ctx.has_bias and need[3]:
-            gb = colsum(gz)
-        return (gx0 if need[0] else None), gx1, gB, gb, None, None
-
-
+# (Every Function below keeps its tensors with save_for_backward, as rsx.dense's do and for its
+# reason: nothing with a grad_fn on ctx.)
 def layer_fwd(a, x, E, Wc, Wl, bl, Wg, bg):
     ops._gpu(a, x, E, Wc, Wl, bl, Wg, bg)
     n, d = x.shape

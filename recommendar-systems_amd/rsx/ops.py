@@ -22,6 +22,11 @@ def _pi(t):
     return 0 if t is None else t.data_ptr()
 
 
+def _arr(ts):
+    """A C array of the tensors' addresses (NULL for None): the pointer-array arguments."""
+    return (C.c_void_p * len(ts))(*[(t.data_ptr() if t is not None else None) for t in ts])
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 

@@ -28,8 +28,9 @@ import torch
 
 from . import _lib as L
 from . import ops
+from .dense import _wgrad
 
-_p = ops._p
+_p, _arr = ops._p, ops._arr
 
 
 # RSX_PREF_SAVED=0: the batch-row preference backward and the gates' backward recompute the
@@ -52,29 +53,12 @@ def _lead_scratch(n_rows: int, device) -> torch.Tensor:
     return t
 
 
-def _arr(ts):
-    return (C.c_void_p * len(ts))(*[(t.data_ptr() if t is not None else None) for t in ts])
-
-
 def supported(d: int) -> bool:
     return d in (64, 128)
 
 
 def _c(t):
     return t if t.is_contiguous() else t.contiguous()
-
-
-def _wgrad(pairs, d, device):
-    """[(dz, x, has_bias)] -> [(dW, db | None)] through rsx_smore_wgrad (<= 8 pairs)."""
-    lib = L.lib()
-    n = pairs[0][0].shape[0]
-    dws = [torch.empty(d, d, dtype=torch.float32, device=device) for _ in pairs]
-    dbs = [torch.empty(d, dtype=torch.float32, device=device) if hb else None for _, _, hb in pairs]
-    ws = torch.empty(max(int(lib.rsx_smore_wgrad_ws_bytes(n, d, len(pairs))), 4), dtype=torch.uint8,
-                     device=device)
-    L.check(lib.rsx_smore_wgrad(len(pairs), _arr([p[0] for p in pairs]), _arr([p[1] for p in pairs]), _arr(dws),
-                                _arr(dbs), n, d, _p(ws), ws.numel(), ops._stream()), "rsx_smore_wgrad")
-    return list(zip(dws, dbs))
 
 
 # ---------------------------------------------------------------------------

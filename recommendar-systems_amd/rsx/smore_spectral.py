@@ -142,7 +142,7 @@ class _ItemSide(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, V, Wv, bv, T, Wt, bt, rv, rt, rf, item, gWv, gbv, gWt, gbt, gWf, gbf, normalize, scale, mul):
-        from .smore_fuse import _arr, _c
+        from .smore_fuse import _c
 
         n, dv = V.shape
         dt = T.shape[1]
@@ -157,7 +157,7 @@ class _ItemSide(torch.autograd.Function):
         lib = L.lib()
         spec = torch.empty(max(int(lib.rsx_smore_spectral_spec_floats(n, d)), 1), device=V.device,
                            dtype=torch.float32)
-        p = ops._p
+        p, _arr = ops._p, ops._arr
         ws = ops._ws(V.device, int(lib.rsx_smore_spectral_fwd_ws_bytes(n, d, dv, dt)))
         L.check(lib.rsx_smore_item_fwd(p(V), dv, p(Wv), p(bv), p(T), dt, p(Wt), p(bt), p(unit[0]), p(unit[1]),
                                        p(unit[2]), n, d, p(img), p(txt), p(cv), p(ct), p(cf), p(spec), p(ws),

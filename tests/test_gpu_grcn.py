@@ -453,7 +453,7 @@ def test_no_autograd_node_outlives_its_step(cuda, tmp_path):
             todo.extend(f for f, _ in fn.next_functions)
         del fn, todo
         # (the nodes of torch's own ops take no weak reference; the Functions' nodes, which are their ctx, do)
-        assert all(any(k in s for s in names) for k in ("_Step", "_Normalize", "_Mlp")), names
+        assert all(any(k in s for s in names) for k in ("_Step", "_Normalize", "_Gemm")), names
         loss.backward()
         del loss
         m.last_terms = None

@@ -1,6 +1,7 @@
 """MMGCN on the GPU: the kernels of csrc/mmgcn.hip (rsx.mmgcn's wrappers) against the float64
 restatement (tests/mmgcn_ref.py) and numpy float64, and the model (rsx.mmgcn.MMGCN) against the
-reference's own run (tests/golden/mmgcn_step0_small.npz, mmgcn_small.npz).
+reference's own run (tests/golden/mmgcn_step0_small.npz, mmgcn_small.npz).  The shared dense
+blocks (the wide product, normalise, the column sum) are tests/test_gpu_dense.py's.
 
 Kernel bound: helpers.check_vs_f32 — 1e-4 of the tensor's scale, or 4x the error the float32
 torch composition of the same ops (on the CPU) makes against the same float64 values, whichever
@@ -19,20 +20,12 @@ import torch
 
 import mmgcn_ref as R
 from helpers import (LOSS_BATCHES, assert_same_run, check_eval, check_params, check_vs_f32, coo_sorted, csr_to_sorted, dev,
-                     loaders, loss_triplets, make_model, quick_start_case, record_batches, train_epochs, write_dataset)
+                     loaders, loss_triplets, make_model, quick_start_case, record_batches, train_epochs, unflagged,
+                     write_dataset)
 
 pytestmark = pytest.mark.gpu
 SHAPES = [(64, 5), (64, 65), (128, 37), (64, 1001)]
 c = lambda t: t.detach().cpu().numpy()  # noqa: E731
-
-
-def _unflagged(pres, n):
-    """[n, 1] float64 mask of the rows no pre-activation of `pres` comes near zero on; at most 5 % flagged."""
-    flag = R.near_zero_rows(pres)
-    share = float(flag.float().mean())
-    print(f"  flagged rows: {int(flag.sum())} of {n} ({share:.3%})")
-    assert share <= 0.05
-    return (~flag).double()[:, None]
 
 
 # ------------------------------------------------------------- the fused layer
@@ -45,7 +38,7 @@ def test_fused_layer_vs_restatement(cuda, d, n):
     x64 = {k: v.double() for k, v in x32.items()}  # the float32 inputs, exactly
     k = {}
     out64 = R.layer(**x64, keep=k)
-    keep = _unflagged([k["ph"], k["pu"], k["po"]], n)
+    keep = unflagged([k["ph"], k["pu"], k["po"]], n)
     go = torch.randn(n, d, dtype=torch.float64, generator=torch.Generator().manual_seed(7)).float().double() * keep
     ref = R.layer_backward(go, **x64)
     kt = {}
@@ -62,117 +55,6 @@ def test_fused_layer_vs_restatement(cuda, d, n):
     out.backward(dev(go.float().numpy(), cuda))
     for name, t in (("g_a", a), ("g_x", x), ("dWc", W[0]), ("dWl", W[1]), ("dbl", W[2]), ("dWg", W[3]), ("dbg", W[4])):
         check_vs_f32(name, c(t.grad), ref[name], tor[name])
-
-
-# ------------------------------------------------------------ the wide product
-# (K or (K0, K1), N, B given [K, N], n, leaky): each extreme of K, N, n, both layouts, the two-segment input
-GEMM_CASES = [(32, 32, False, 5, False), (32, 256, True, 65, True), (96, 96, False, 1001, True), (96, 32, True, 5, False),
-              (256, 256, True, 65, True), (256, 96, False, 1001, False), (384, 256, False, 65, True),
-              (384, 32, True, 1001, True), (384, 96, True, 5, True), ((96, 64), 96, False, 65, True),
-              ((96, 64), 256, True, 1001, False), (32, 96, False, 1001, True)]
-
-
-@pytest.mark.parametrize("K,N,b_kn,n,act", GEMM_CASES, ids=lambda v: str(v).replace(" ", ""))
-def test_wide_product_and_its_gradients_vs_float64(cuda, K, N, b_kn, n, act):
-    from rsx import mmgcn as M
-
-    ks = K if isinstance(K, tuple) else (K,)
-    Kt = sum(ks)
-    rng = np.random.default_rng(1000 + Kt + N + n)
-    f32 = lambda a: a.astype(np.float32)  # noqa: E731
-    xs = [f32(rng.standard_normal((n, k)) * 0.5) for k in ks]
-    B = f32(rng.standard_normal((Kt, N) if b_kn else (N, Kt)) / np.sqrt(Kt))
-    b = f32(rng.standard_normal(N) * 0.1)
-
-    def compose(dtype, go=None):
-        t = lambda a: torch.from_numpy(a).to(dtype).requires_grad_(True)  # noqa: E731
-        X, Bt, bt = [t(a) for a in xs], t(B), t(b)
-        pre = torch.cat(X, dim=1) @ (Bt if b_kn else Bt.t()) + bt
-        y = R.leaky(pre) if act else pre
-        if go is not None:
-            (y * go.to(dtype)).sum().backward()
-        return pre.detach(), y.detach(), [a.grad for a in X], Bt.grad, bt.grad
-
-    pre64 = compose(torch.float64)[0]
-    keep = _unflagged([pre64], n) if act else torch.ones(n, 1, dtype=torch.float64)
-    go = torch.from_numpy(f32(rng.standard_normal((n, N)))).double() * keep
-    _, y64, gx64, gB64, gb64 = compose(torch.float64, go)
-    _, y32, gx32, gB32, gb32 = compose(torch.float32, go)
-    X = [dev(a, cuda, True) for a in xs]
-    Bd, bd = dev(B, cuda, True), dev(b, cuda, True)
-    y = M._Gemm.apply(X[0], X[1] if len(X) > 1 else None, Bd, bd, b_kn, act)
-    check_vs_f32("y", c(y), y64, y32)
-    y.backward(dev(go.float().numpy(), cuda))
-    for j, t in enumerate(X):
-        check_vs_f32(f"dX{j}", c(t.grad), gx64[j], gx32[j])
-    check_vs_f32("dB", c(Bd.grad), gB64, gB32)
-    check_vs_f32("db", c(bd.grad), gb64, gb32)
-
-
-def test_wide_product_epilogues(cuda):
-    """The residual output (y and y + r from one launch), the output mask, the masked input rows."""
-    from rsx import mmgcn as M
-
-    rng = np.random.default_rng(5)
-    f32 = lambda a: a.astype(np.float32)  # noqa: E731
-    n, K, N = 65, 96, 64
-    x, W, b, r, m = (f32(rng.standard_normal(s)) for s in ((n, K), (N, K), (N,), (n, N), (n, N)))
-    saved = f32(rng.standard_normal((n, K)))
-    X, Wd, bd, Rd, Md, Sd = (dev(a, cuda) for a in (x, W, b, r, m, saved))
-    want = R.leaky(torch.from_numpy(x).double() @ torch.from_numpy(W).double().t() + torch.from_numpy(b).double())
-    u, xh = M.gemm(X, Wd, N, False, bias=bd, act=True, r=Rd)
-    check_vs_f32("u", c(u), want, want.float())
-    assert torch.equal(xh, u + Rd)
-    masked = M.gemm(X, Wd, N, False, bias=bd, act=True, my=Md)
-    assert torch.equal(masked, torch.where(Md > 0, u, u * np.float32(0.01)))
-    xm = torch.empty_like(X)
-    y = M.gemm(X, Wd, N, False, mx=Sd, xm_out=xm)
-    assert torch.equal(xm, torch.where(Sd > 0, X, X * np.float32(0.01)))
-    assert torch.equal(y, M.gemm(xm, Wd, N, False))
-    for bad in (dict(n_out=40), dict(k=6)):
-        with pytest.raises(RuntimeError, match="RSX_ERR_UNSUPPORTED"):
-            if "k" in bad:
-                M.gemm(dev(x[:, :6].copy(), cuda), dev(W[:, :6].copy(), cuda), N, False)
-            else:
-                M.gemm(X, dev(W[:40].copy(), cuda), 40, False)
-
-
-# ------------------------------------------------------------------ normalise
-@pytest.mark.parametrize("n,w", [(5, 256), (67, 256), (130, 32), (9, 384)])
-def test_normalize_forward_and_gradient(cuda, n, w):
-    from rsx import mmgcn as M
-
-    rng = np.random.default_rng(n + w)
-    x = rng.standard_normal((n, w)).astype(np.float32)
-    x[n // 2] = 0.0  # an all-zero row: zeros out, g / 1e-12 back (the clamp passes nothing through the norm)
-    g = rng.standard_normal((n, w)).astype(np.float32) * 1e-6
-    res = {}
-    for dtype in (torch.float64, torch.float32):
-        t = torch.from_numpy(x).to(dtype).requires_grad_(True)
-        y = torch.nn.functional.normalize(t)
-        y.backward(torch.from_numpy(g).to(dtype))
-        res[dtype] = (y.detach(), t.grad)
-    X = dev(x, cuda, True)
-    y = M._Normalize.apply(X)
-    assert not c(y)[n // 2].any()
-    y.backward(dev(g, cuda))
-    check_vs_f32("y", c(y), *(res[k][0] for k in res))
-    rest = np.arange(n) != n // 2  # (the zero row's gradient is 1e12 times the others': checked apart)
-    check_vs_f32("g_x", c(X.grad)[rest], *(res[k][1][rest] for k in res))
-    check_vs_f32("g_x, zero row", c(X.grad)[~rest], *(res[k][1][~rest] for k in res))
-    # in place, as the image branch writes its item rows
-    buf = dev(x, cuda)
-    y2, _ = M.normalize_fwd(buf, out=buf)
-    assert torch.equal(y2, y.detach())
-
-
-def test_colsum_is_ordered(cuda):
-    from rsx import mmgcn as M
-
-    g = torch.from_numpy(np.random.default_rng(2).standard_normal((1001, 320)).astype(np.float32))
-    got = M.colsum(g.to(cuda))
-    check_vs_f32("colsum", c(got), g.double().sum(0), g.sum(0))
-    assert torch.equal(got, M.colsum(g.to(cuda)))
 
 
 # ----------------------------------------------------------------------- loss

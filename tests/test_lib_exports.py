@@ -52,17 +52,19 @@ def test_struct_layouts_match_header(tmp_path):
 
 
 def test_blocks_import_no_model():
-    """rsx.blocks is what the models share: importing it (in a fresh interpreter) loads no
-    model module."""
+    """rsx.blocks and rsx.dense are what the models share: importing either (in a fresh
+    interpreter) loads no model module."""
     import subprocess
     import sys
 
     import rsx
 
-    models = ("smore", "bm3", "mgcn", "freedom", "lattice", "lightgcn", "layergcn", "mf")
-    code = (f"import sys; sys.path.insert(0, {os.path.dirname(os.path.dirname(rsx.__file__))!r}); import rsx.blocks; "
-            f"bad = [m for m in {models!r} if 'rsx.' + m in sys.modules]; assert not bad, bad")
-    subprocess.run([sys.executable, "-c", code], check=True)
+    models = ("smore", "bm3", "mgcn", "freedom", "lattice", "lightgcn", "layergcn", "mf", "lgmrec", "mmgcn", "grcn",
+              "dualgnn", "smore_fuse", "mgcn_fuse")
+    for shared in ("rsx.blocks", "rsx.dense"):
+        code = (f"import sys; sys.path.insert(0, {os.path.dirname(os.path.dirname(rsx.__file__))!r}); import {shared}; "
+                f"bad = [m for m in {models!r} if 'rsx.' + m in sys.modules]; assert not bad, bad")
+        subprocess.run([sys.executable, "-c", code], check=True)
 
 
 def test_comm_unique_id_size():

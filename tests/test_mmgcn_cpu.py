@@ -259,10 +259,8 @@ def test_library_symbols_and_limits():
     from rsx import _lib as L
 
     lib = L.lib()
-    for name in ("rsx_mmgcn_layer_fwd", "rsx_mmgcn_layer_bwd", "rsx_mmgcn_gemm", "rsx_mmgcn_normalize_fwd",
-                 "rsx_mmgcn_normalize_bwd", "rsx_mmgcn_colsum_ws_bytes", "rsx_mmgcn_colsum", "rsx_mmgcn_loss_ws_bytes",
-                 "rsx_mmgcn_loss_fwd", "rsx_mmgcn_loss_bwd"):
+    for name in ("rsx_mmgcn_layer_fwd", "rsx_mmgcn_layer_bwd", "rsx_mmgcn_loss_ws_bytes", "rsx_mmgcn_loss_fwd",
+                 "rsx_mmgcn_loss_bwd"):
         assert hasattr(lib, name) and name in L.EXPORTED, name
     assert lib.rsx_mmgcn_loss_ws_bytes(512, 64) > 0 and lib.rsx_mmgcn_loss_ws_bytes(65536, 128) > 0
     assert lib.rsx_mmgcn_loss_ws_bytes(65537, 64) == 0 and lib.rsx_mmgcn_loss_ws_bytes(512, 32) == 0
-    assert lib.rsx_mmgcn_colsum_ws_bytes(1001, 256) == 8 * 256 * 4

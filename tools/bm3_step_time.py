@@ -127,7 +127,8 @@ def main():
     opt = Trainer(c, m).optimizer
     names = ("prop_fwd", "proj_fwd", "loss_fwd_bwd", "proj_bwd", "prop_bwd", "adam")
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
-    from rsx.blocks import _ego, _Project, _PropMean
+    from rsx.blocks import _ego, _PropMean
+    from rsx.dense import _Project
 
     def one_step(it):
         opt.zero_grad(set_to_none=True)

@@ -36,8 +36,7 @@ def main():
     from rsx import _lib as L
     from rsx import dualgnn as M
     from rsx import ops
-    from rsx.grcn import _Mlp
-    from rsx.mmgcn import _Gemm, _Normalize
+    from rsx.dense import _Gemm, _Normalize
     from rsx.optim import RsxAdam
 
     m, c, batches, n_edges = synth_model("DualGNN", "baby", args, dict(learning_rate=0.001, reg_weight=0.001,
@@ -68,16 +67,19 @@ def main():
         return run
 
     mods = m._mods()
+
+    def mlp2(g, f):
+        hid = _Gemm.apply(f, None, g.MLP.weight, g.MLP.bias, False, True)
+        return _Gemm.apply(hid, None, g.MLP_1.weight, g.MLP_1.bias, False, False)
+
     with torch.no_grad():
-        xn = {k: _Normalize.apply(torch.cat([g.preference, _Gemm.apply(_Mlp.apply(f, g.MLP.weight, g.MLP.bias), None,
-                                                                         g.MLP_1.weight, g.MLP_1.bias, False, False)]))
-              for k, g, f in mods}
+        xn = {k: _Normalize.apply(torch.cat([g.preference, mlp2(g, f)])) for k, g, f in mods}
         xh = {k: M.propagate(m.A, x) for k, x in xn.items()}
 
     def mlp():
         out = 0
         for k, g, f in mods:
-            temp = _Gemm.apply(_Mlp.apply(f, g.MLP.weight, g.MLP.bias), None, g.MLP_1.weight, g.MLP_1.bias, False, False)
+            temp = mlp2(g, f)
             out = out + _Normalize.apply(torch.cat([g.preference, temp], dim=0)).sum()
         return out
 

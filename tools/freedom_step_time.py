@@ -76,7 +76,8 @@ def main():
     args = parser(steps=100, warmup=20).parse_args()
     require_gpu("freedom_step_time", args)
     from rsx import freedom
-    from rsx.blocks import _ego, _Project, ui_backbone
+    from rsx.blocks import _ego, ui_backbone
+    from rsx.dense import _Project
     from rsx.optim import RsxAdam
 
     fused = freedom._FreedomLoss

@@ -11,7 +11,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "recommendar-systems_amd"))
 from rsx import _lib as L  # noqa: E402
 from rsx import ops  # noqa: E402
-from rsx.smore_fuse import _arr  # noqa: E402
+from rsx.ops import _arr  # noqa: E402
 
 
 def run(n, dv, dt, d, iters=50):

@@ -83,7 +83,8 @@ def main():
     from rsx import mgcn
     from rsx import mgcn_fuse as MF
     from rsx import smore_fuse as SF
-    from rsx.blocks import _ego, _Project, ui_backbone
+    from rsx.blocks import _ego, ui_backbone
+    from rsx.dense import _Project
     from rsx.trainer import Trainer
 
     m, c, batches, _ = synth_model("MGCN", "sports", args, dict(cl_loss=0.01, is_multimodal_model=True),

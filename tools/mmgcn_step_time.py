@@ -32,6 +32,7 @@ def main():
     require_gpu("mmgcn_step_time", args)
     import mmgcn_ref as R
     from rsx import mmgcn as M
+    from rsx.dense import _Gemm
     from rsx.optim import RsxAdam
 
     m, c, batches, n_edges = synth_model("MMGCN", "baby", args, dict(learning_rate=0.001, reg_weight=0.001,
@@ -59,12 +60,12 @@ def main():
         return run
 
     with torch.no_grad():
-        x0v = M._ImageRows.apply(M._Gemm.apply(m.v_feat, None, v.MLP.weight, v.MLP.bias, False, False), m._x0["v"][0])
+        x0v = M._ImageRows.apply(_Gemm.apply(m.v_feat, None, v.MLP.weight, v.MLP.bias, False, False), m._x0["v"][0])
         x1 = M._Layer1.apply(G, None, x0v, E, *v.layer(1))
     x0t, a0t = m._x0["t"]
 
     def mlp():
-        temp = M._Gemm.apply(m.v_feat, None, v.MLP.weight, v.MLP.bias, False, False)
+        temp = _Gemm.apply(m.v_feat, None, v.MLP.weight, v.MLP.bias, False, False)
         return M._ImageRows.apply(temp, m._x0["v"][0]).sum()
 
     def layers23():
