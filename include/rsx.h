@@ -1890,6 +1890,65 @@ int rsx_dualgnn_loss_fwd(const rsx_dualgnn_loss_args* a, float* out, void* ws, s
 int rsx_dualgnn_loss_bwd(const rsx_dualgnn_loss_args* a, const float* go, float* g_result, float* g_pref_v,
                          float* g_pref_t, float* g_weight_i, void* ws, size_t ws_bytes, rsx_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* DRAGON: 128-wide concatenation, user graph, loss (dragon.hip)              */
+/* ------------------------------------------------------------------------ */
+/*
+ * DRAGON (reference src/models/dragon.py) is DualGNN with the two 64-wide modality tables
+ * concatenated (construction = 'cat') and a frozen item-item graph on the item rows (rsx_spmm).
+ * f32, deterministic and free of atomics; tables 16-byte aligned (else RSX_ERR_ARG); caller-owned
+ * buffers, no allocation or synchronisation; stream-ordered, graph-capturable.  n = n_users +
+ * n_items < 2^31.
+ *
+ * The concatenation (dragon.py:231-245), one pass over xv, xt [n, 64] (both required);
+ * weight_u [n_users, 2]:
+ *   user rows   user_rep[u] = [w0 v[u] | w1 t[u]]          -> user_rep [n_users, 128]
+ *   item rows   [v[i] | t[i]]                              -> item_rep [n_items, 128]
+ * rsx_dragon_cat_bwd, from g_user_rep [n_users, 128] and g_item_rep [n_items, 128]:
+ *   g_v, g_t [n, 64]: the halves of the gradient rows, the user rows scaled by w0 and w1;
+ *   g_weight_u[u] = (<g_user_rep[u, :64], v[u]>, <g_user_rep[u, 64:], t[u]>)
+ * (the regulariser mean(weight_u^2) is the loss's: rsx_dragon_loss_bwd).
+ */
+int rsx_dragon_cat_fwd(const float* xv, const float* xt, const float* weight_u, int64_t n_users, int64_t n_items,
+                       float* user_rep, float* item_rep, rsx_stream_t stream);
+int rsx_dragon_cat_bwd(const float* g_user_rep, const float* g_item_rep, const float* xv, const float* xt,
+                       const float* weight_u, int64_t n_users, int64_t n_items, float* g_v, float* g_t,
+                       float* g_weight_u, rsx_stream_t stream);
+/*
+ * The user graph (dragon.py:251-252, 327-341): rsx_dualgnn_ugraph_fwd at d = 64 or 128 (else
+ * RSX_ERR_UNSUPPORTED): out[u] = user_rep[u] + sum_{j < k} W[u, j] user_rep[idx[u, j]], j
+ * ascending; 1 <= k <= 64.  An index outside [0, n_users) contributes nothing.  out may be a
+ * taller table (its first n_users rows are written) and must not be user_rep (RSX_ERR_ARG).  The
+ * backward is g + P^T g on rsx_spmm over the transposed lists.
+ */
+int rsx_dragon_ugraph_fwd(const float* user_rep, const int32_t* idx, const float* W, int64_t n_users, int32_t k,
+                          int32_t d, float* out, rsx_stream_t stream);
+/*
+ * The loss (dragon.py:262-277) on result [n, d] (user row u, item row n_users + i), d = 128 (the
+ * concatenation: pref_v, pref_t, either may be NULL) or d = 64 (one modality: exactly one of
+ * pref_v, pref_t); the preference tables are [n_users, 64] at either d; x_b the BPR score
+ * difference:
+ *   out = {bpr + reg, bpr, reg},  bpr = mean softplus(-x_b) / ln 2   (-mean log2 sigmoid)
+ *   reg = reg_weight (sum_b |pref_v[u_b]|^2 / (batch 64) + sum_b |pref_t[u_b]|^2 / (batch 64))
+ *         + reg_weight mean(weight_u^2)                   (no weight_i term)
+ * The backward writes EVERY row of g_result [n, d] (zero off the batch, repeated rows summed by
+ * the first-occurrence walk), of g_pref_v, g_pref_t [n_users, 64] (2 reg_weight / (batch 64)
+ * count(u) pref_m[u], count the user's occurrences in the batch) and g_weight_u = 2 reg_weight /
+ * (2 n_users) weight_u [n_users, 2].  go: the upstream gradient, a device word.  1 <= batch <=
+ * 65536; ws >= rsx_dragon_loss_ws_bytes(batch, d) (0: unsupported).
+ */
+typedef struct rsx_dragon_loss_args {
+    const float *result, *pref_v, *pref_t, *weight_u;
+    const int64_t* triplets; /* [3, batch] users, positives, negatives (item ids, not offset) */
+    int64_t n_users, n_items, batch;
+    int32_t d;
+    float reg_weight;
+} rsx_dragon_loss_args;
+size_t rsx_dragon_loss_ws_bytes(int64_t batch, int32_t d);
+int rsx_dragon_loss_fwd(const rsx_dragon_loss_args* a, float* out, void* ws, size_t ws_bytes, rsx_stream_t stream);
+int rsx_dragon_loss_bwd(const rsx_dragon_loss_args* a, const float* go, float* g_result, float* g_pref_v,
+                        float* g_pref_t, float* g_weight_u, void* ws, size_t ws_bytes, rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

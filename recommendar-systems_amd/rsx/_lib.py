@@ -169,6 +169,11 @@ class DualgnnLossArgs(C.Structure):
                 ("n_users", I64), ("n_items", I64), ("batch", I64), ("d", I32), ("reg_weight", F32)]
 
 
+class DragonLossArgs(C.Structure):
+    _fields_ = [("result", P), ("pref_v", P), ("pref_t", P), ("weight_u", P), ("triplets", P), ("n_users", I64),
+                ("n_items", I64), ("batch", I64), ("d", I32), ("reg_weight", F32)]
+
+
 class LatticeGraph(C.Structure):
     _fields_ = [("n", I64), ("k", I32), ("n_mod", I32), ("f", I32), ("lam", F32), ("F", P * 2), ("idx", P * 2),
                 ("oidx", P * 2), ("oval", P * 2), ("modal_weight", P), ("w", P), ("invn", P * 2), ("a", P * 2),
@@ -342,6 +347,12 @@ def _declare(lib):
         "rsx_dualgnn_loss_ws_bytes": (C.c_size_t, [I64, I32]),
         "rsx_dualgnn_loss_fwd": (C.c_int, [C.POINTER(DualgnnLossArgs), P, P, C.c_size_t, P]),
         "rsx_dualgnn_loss_bwd": (C.c_int, [C.POINTER(DualgnnLossArgs), P, P, P, P, P, P, C.c_size_t, P]),
+        "rsx_dragon_cat_fwd": (C.c_int, [P, P, P, I64, I64, P, P, P]),
+        "rsx_dragon_cat_bwd": (C.c_int, [P, P, P, P, P, I64, I64, P, P, P, P]),
+        "rsx_dragon_ugraph_fwd": (C.c_int, [P, P, P, I64, I32, I32, P, P]),
+        "rsx_dragon_loss_ws_bytes": (C.c_size_t, [I64, I32]),
+        "rsx_dragon_loss_fwd": (C.c_int, [C.POINTER(DragonLossArgs), P, P, C.c_size_t, P]),
+        "rsx_dragon_loss_bwd": (C.c_int, [C.POINTER(DragonLossArgs), P, P, P, P, P, P, C.c_size_t, P]),
         "rsx_cpu_spmm": (C.c_int, [P, P, P, I64, P, I32, P]),
         "rsx_cpu_propagate_mean": (C.c_int, [P, P, P, I64, P, I32, I32, P]),
         "rsx_cpu_layergcn_forward": (C.c_int, [P, P, P, I64, P, I32, I32, P, P, P]),
@@ -394,6 +405,8 @@ EXPORTED = ["rsx_version", "rsx_csr_schedule_host", "rsx_csr_schedule_rebind", "
             "rsx_grcn_refine_bwd", "rsx_grcn_loss_ws_bytes", "rsx_grcn_loss_fwd", "rsx_grcn_loss_bwd",
             "rsx_dualgnn_mix_fwd", "rsx_dualgnn_mix_bwd", "rsx_dualgnn_ugraph_fwd", "rsx_dualgnn_loss_ws_bytes",
             "rsx_dualgnn_loss_fwd", "rsx_dualgnn_loss_bwd",
+            "rsx_dragon_cat_fwd", "rsx_dragon_cat_bwd", "rsx_dragon_ugraph_fwd", "rsx_dragon_loss_ws_bytes",
+            "rsx_dragon_loss_fwd", "rsx_dragon_loss_bwd",
             "rsx_cpu_spmm", "rsx_cpu_propagate_mean", "rsx_cpu_layergcn_forward", "rsx_cpu_layergcn_backward",
             "rsx_cpu_bpr", "rsx_cpu_fullsort_topk", "rsx_cpu_adam", "rsx_cpu_gcn_step_ws_floats", "rsx_cpu_gcn_step"]
 

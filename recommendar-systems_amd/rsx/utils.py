@@ -13,7 +13,8 @@ MODELS = {"lightgcn": ("rsx.lightgcn", "LightGCN"), "layergcn": ("rsx.layergcn",
           "bm3": ("rsx.bm3", "BM3"), "mgcn": ("rsx.mgcn", "MGCN"),
           "freedom": ("rsx.freedom", "FREEDOM"), "lattice": ("rsx.lattice", "LATTICE"),
           "lgmrec": ("rsx.lgmrec", "LGMRec"), "mmgcn": ("rsx.mmgcn", "MMGCN"),
-          "grcn": ("rsx.grcn", "GRCN"), "dualgnn": ("rsx.dualgnn", "DualGNN")}
+          "grcn": ("rsx.grcn", "GRCN"), "dualgnn": ("rsx.dualgnn", "DualGNN"),
+          "dragon": ("rsx.dragon", "DRAGON")}
 
 
 def get_local_time():

@@ -13,15 +13,15 @@ modifies a reference file:
    `src/models/mgcn.py:59,69`, `src/models/lattice.py:76,87`);
 4. `torch_scatter.scatter_add` is restated with `index_add_` (`src/utils/utils.py:140`).
 
-GRCN, MMGCN and DualGNN add a fifth for their own captures: `torch_geometric` as far as
-`src/models/grcn.py`, `src/models/mmgcn.py` and `src/models/dualgnn.py` use it (`_install_pyg_shim`).
-DualGNN's capture also runs the reference's user-graph generator and moves `result_embed` out of
-the CPU model's parameters (`_dualgnn_user_graph`, `_dualgnn_model`).
+GRCN, MMGCN, DualGNN and DRAGON add a fifth for their own captures: `torch_geometric` as far as
+`src/models/grcn.py`, `src/models/mmgcn.py`, `src/models/dualgnn.py` and `src/models/dragon.py` use it
+(`_install_pyg_shim`).  DualGNN's and DRAGON's captures also run the reference's user-graph generator
+and move `result_embed` out of the CPU model's parameters (`_dualgnn_user_graph`, `_dualgnn_model`).
 
 Outputs are small `.npz` files under `tests/golden/` (data only: inputs and the
 reference's outputs). The reference itself never travels to the GPU box.
 
-Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn | dualgnn]
+Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn | dualgnn | dragon]
 """
 from __future__ import annotations
 
@@ -1519,20 +1519,21 @@ def _dualgnn_user_graph(inter_path: str, out_path: str):
     return d, graph.numpy()
 
 
-def _dualgnn_model():
-    """The reference's DualGNN on the CPU.  Its constructor leaves `result_embed` registered as a
-    float64 Parameter there (`.to(device)` of the same device returns the Parameter itself), and
+def _dualgnn_model(name="DualGNN"):
+    """The reference's DualGNN (or DRAGON, whose constructor does the same) on the CPU.  It leaves
+    `result_embed` registered as a float64 Parameter there (`.to(device)` of the same device
+    returns the Parameter itself), and
     the first forward then cannot assign a tensor under that name; on a GPU it is a plain tensor.
     It is popped from `_parameters` and set back as a plain tensor before the Trainer and its
     optimiser are made.  Nothing in the reference is edited."""
     from utils.utils import init_seed, get_model
     from common.trainer import Trainer
 
-    config, train, valid, test = _load("DualGNN", "baby", GRCN_OVERRIDES)
+    config, train, valid, test = _load(name, "baby", GRCN_OVERRIDES)
     hp = _select_hparams(config)
     init_seed(config["seed"])
     train.pretrain_setup()
-    model = get_model("DualGNN")(config, train)
+    model = get_model(name)(config, train)
     emb = model._parameters.pop("result_embed")
     assert emb.dtype == torch.float64
     model.result_embed = emb.detach().clone()
@@ -1705,10 +1706,238 @@ def capture_dualgnn(out_dir):
         assert os.path.getsize(os.path.join(out_dir, f)) < (1 << 20), f
 
 
+DRAGON_ROWS = dict(rep=8, grad=2, param=4, const=8, epoch=8, last=4)  # row strides of the stored tables
+DRAGON_SEEDS = dict(v=41, t=42)  # feature seeds at which the capture's two margins hold
+
+
+def _knn_margin(feat: torch.Tensor, k: int):
+    """(smallest gap between a row's k-th and (k+1)-th cosine similarity, twice the largest
+    float32-vs-float64 difference on the matrix), the float32 matrix as dragon.py:159-160 forms it."""
+    xn = feat.div(torch.norm(feat, p=2, dim=-1, keepdim=True))
+    sim32 = torch.mm(xn, xn.transpose(1, 0))
+    f64 = feat.double()
+    xn64 = f64.div(torch.norm(f64, p=2, dim=-1, keepdim=True))
+    sim64 = torch.mm(xn64, xn64.transpose(1, 0))
+    srt = torch.sort(sim32, dim=-1, descending=True)[0]
+    return float((srt[:, k - 1] - srt[:, k]).min()), 2.0 * float((sim32.double() - sim64).abs().max())
+
+
+def capture_dragon(out_dir):
+    """DRAGON (reference src/models/dragon.py) on the small graph, 48-wide image and 32-wide text
+    features: seed 999, the YAML's sizes (knn_k 10, n_mm_layers 1, mm_image_weight 0.1),
+    learning_rate and reg_weight 0.001, batches of 512; the user graph from the reference's own
+    generator.  torch_geometric is the shim above; `result_embed` is popped as for DualGNN.
+    dragon_step0_small.npz: the first two steps: triplets, loss / bpr / reg (bpr and reg in
+    float64 on the model's own tensors; they have to account for the loss), step 0's x_hat of
+    either modality, user_rep, result and every gradient, the parameters after either step; the
+    two margins (below).
+    dragon_small.npz: the user lists as flat arrays, the two epochs' sampled lists and weights,
+    mm_adj as COO, the initial parameters and result_embed, the features, two epochs through the
+    reference's Trainer with the parameters after each, the evaluation of the initial table and of
+    the last epoch; and epoch{e}_f32_dist.<name>: how far the reference's float32 parameters are,
+    after each epoch, from the float64 restatement (tests/dragon_ref.py) trained on the same
+    batches and lists.
+    The capture fails unless (a) at step 0 every leaky_relu pre-activation of the reference is
+    farther from zero than twice the largest difference, on that tensor, between the reference's
+    float32 pre-activation and the float64 restatement's, and (b) in every row of either
+    modality's cosine matrix the knn_k-th and (knn_k+1)-th similarities differ by more than twice
+    the largest float32-vs-float64 difference on that matrix: a float32 top-k by any summation
+    order then names the same neighbours."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import dragon_ref as R
+
+    shutil.rmtree(os.path.join(DATA_ROOT, "baby"), ignore_errors=True)
+    df = synth.amazon_like(400, 200, 4000, seed=7)
+    synth.write_inter(df, DATA_ROOT, "baby")
+    n_items = int(df.itemID.max()) + 1
+    base = os.path.join(DATA_ROOT, "baby")
+    np.save(os.path.join(base, "image_feat_raw.npy"), synth.features(n_items, 48, seed=DRAGON_SEEDS["v"]))
+    np.save(os.path.join(base, "text_feat_raw.npy"), synth.features(n_items, 32, seed=DRAGON_SEEDS["t"]))
+    lists, _ = _dualgnn_user_graph(os.path.join(base, "baby.inter"), os.path.join(base, "user_graph_dict.npy"))
+    _install_pyg_shim()
+    S = DRAGON_ROWS
+
+    def fresh_model():
+        for f in os.listdir(base):  # the reference's own cache: every model of the capture builds mm_adj itself
+            if f.startswith("mm_adj_"):
+                os.remove(os.path.join(base, f))
+        return _dualgnn_model("DRAGON")
+
+    # ---- pass 1: the first two steps
+    config, hp, train, valid, test, model, trainer = fresh_model()
+    nu, ni = model.n_users, model.n_items
+    names = tuple(n for n, _ in model.named_parameters())
+    assert names == R.names(), names
+    # the constructed model's names throughout (the first forward registers the preferences under
+    # a second name, as DualGNN's does)
+    fixed = lambda mdl: [(n, p) for n, p in zip(names, [q for _, q in mdl.named_parameters()])]  # noqa: E731
+    params = fixed(model)
+    init = {n: p.detach().numpy().copy() for n, p in params}
+    result0 = model.result_embed.numpy().copy()
+    feats32 = {"v": model.v_feat, "t": model.t_feat}
+    layers, knn_k = int(model.n_layers), int(model.knn_k)
+    out = {"n_users": np.int64(nu), "n_items": np.int64(ni)}
+    for m in R.MODS:
+        gap, thr = _knn_margin(feats32[m], knn_k)
+        assert gap > thr, f"{m}: a top-{knn_k} boundary gap of {gap:.3e}, float32 vs float64 {thr:.3e}: pick other feature seeds"
+        print(f"kNN margin {m}: smallest gap {gap:.3e}, threshold {thr:.3e}")
+        out[f"knn_gap_min.{m}"], out[f"knn_gap_thr.{m}"] = np.float64(gap), np.float64(thr)
+    mm = model.mm_adj.coalesce()
+    mm_idx, mm_val = mm.indices().numpy().copy(), mm.values().numpy().astype(np.float32).copy()
+    mm64 = torch.zeros(ni, ni, dtype=torch.float64)
+    mm64[mm_idx[0], mm_idx[1]] = torch.from_numpy(mm_val).double()
+    ei = model.edge_index.numpy()
+    E = ei.shape[1] // 2
+    train_u, train_i = ei[0, :E], ei[1, :E] - nu
+    A64 = R.sym_operator(train_u, train_i, nu, ni)
+    taps = {}
+    for m, g in (("v", model.v_gcn), ("t", model.t_gcn)):
+        g.MLP.register_forward_hook(lambda _m, _i, o, key=("pre", m): taps.__setitem__(key, o.detach().clone()))
+        g.register_forward_hook(lambda _m, _i, o, key=("x_hat", m): taps.__setitem__(key, o[0].detach().clone()))
+    model.user_graph.register_forward_hook(lambda _m, i, _o: taps.__setitem__("user_rep", i[0].detach().clone()))
+    model.pre_epoch_processing()
+    idx0 = np.asarray(model.epoch_user_graph, dtype=np.int64)
+    W0 = model.user_weight_matrix.numpy().copy()
+    P64 = R.cast({n: torch.from_numpy(v) for n, v in init.items()}, torch.float64)
+    f64 = {m: f.double() for m, f in feats32.items()}
+    model.train()
+    it = iter(train)
+    for step in range(2):
+        batch = next(it)
+        trip = batch.clone()  # the reference's forward offsets the item rows of the batch in place
+        trainer.optimizer.zero_grad()
+        loss = model.calculate_loss(batch)
+        loss.backward()
+        pre = f"step{step}_"
+        rep = model.result_embed.detach()
+        assert rep.shape == (nu + ni, 128)
+        if step == 0:
+            keep = {}
+            with torch.no_grad():
+                R.forward(P64, f64, A64, mm64, layers, idx0, torch.from_numpy(W0).double(), nu, keep)
+            margin, worst = np.inf, 0.0
+            for m in R.MODS:
+                p32, p64 = taps[("pre", m)], keep[m]["pre"]
+                diff = float((p32.double() - p64).abs().max())
+                near = float(p32.abs().min())
+                assert near > 2 * diff, f"{m}: a pre-activation at {near:.3e}, reference vs restatement {diff:.3e}: pick other feature seeds"
+                margin, worst = min(margin, near / diff), max(worst, diff)
+                out[f"step0_preact_min.{m}"] = np.float64(near)
+                out[f"step0_preact_thr.{m}"] = np.float64(2 * diff)
+            print(f"pre-activations: smallest |pre| / (reference - restatement) = {margin:.1f} (needs > 2), largest "
+                  f"difference {worst:.3e}")
+            out["step0_x_hat_v"] = taps[("x_hat", "v")].numpy()[::S["rep"]].copy()
+            out["step0_x_hat_t"] = taps[("x_hat", "t")].numpy()[::S["rep"]].copy()
+            out["step0_user_rep"] = taps["user_rep"].numpy()[::S["rep"]].copy()
+            out["step0_result"] = rep.numpy()[::S["rep"]].copy()
+        u, p, n = trip[0], trip[1] + nu, trip[2] + nu
+        r64 = rep.double()
+        bpr = torch.nn.functional.softplus(-((r64[u] * r64[p]).sum(1) - (r64[u] * r64[n]).sum(1))).mean() / np.log(2.0)
+        reg = float(model.reg_weight) * sum((t.detach().double() ** 2).mean() for t in (
+            model.v_gcn.preference[u], model.t_gcn.preference[u], model.weight_u))
+        assert abs(loss.item() - bpr.item() - reg.item()) <= 3e-6 * abs(loss.item()), (loss.item(), bpr.item(), reg.item())
+        out[pre + "triplets"] = trip.numpy().astype(np.int16)
+        out[pre + "loss"], out[pre + "bpr"], out[pre + "reg"] = (np.float64(v.item()) for v in (loss, bpr, reg))
+        no_grad = []
+        for name, prm in params:
+            if prm.grad is None:
+                no_grad.append(name)
+            else:
+                out[pre + "grad." + name] = R.rows(_flat2(prm.grad.numpy()), S["grad"]).copy()
+        assert tuple(sorted(no_grad)) == tuple(sorted(R.UNUSED)), no_grad
+        trainer.optimizer.step()
+        for name, prm in params:
+            if name in R.UNUSED:  # no gradient, no update: the initial value, which dragon_small.npz holds
+                assert np.array_equal(prm.detach().numpy(), init[name]), name
+            else:
+                out[pre + "param." + name] = R.rows(_flat2(prm.detach().numpy()), S["param"]).copy()
+    out["no_grad"] = np.array(no_grad)
+    out["row_strides"] = np.array([f"{k}={v}" for k, v in S.items()])
+    out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()] +
+                              [f"{k}={config[k]}" for k in ("embedding_size", "n_mm_layers", "knn_k", "mm_image_weight")])
+    path = os.path.join(out_dir, "dragon_step0_small.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}: {os.path.getsize(path) / 1e6:.2f} MB, keys={len(out)}")
+
+    # ---- pass 2: two epochs through the reference's Trainer, the float64 restatement beside it
+    config, hp, train, valid, test, model, trainer = fresh_model()
+    params = fixed(model)
+    for n, p in params:
+        assert np.array_equal(p.detach().numpy(), init[n]), n
+    assert np.array_equal(model.result_embed.numpy(), result0)
+    mm2 = model.mm_adj.coalesce()
+    assert np.array_equal(mm2.indices().numpy(), mm_idx) and np.array_equal(mm2.values().numpy(), mm_val)
+    out = {"n_users": np.int64(nu), "n_items": np.int64(ni)}
+    out["train_u"], out["train_i"] = train_u.astype(np.int16), train_i.astype(np.int16)
+    lens = np.array([len(lists[u][0]) for u in range(nu)], dtype=np.int64)
+    out["ug_ptr"] = np.concatenate([[0], np.cumsum(lens)]).astype(np.int32)
+    out["ug_nbr"] = np.concatenate([np.asarray(lists[u][0], dtype=np.int16) for u in range(nu)])
+    cnt = np.concatenate([np.asarray(lists[u][1], dtype=np.float64) for u in range(nu)])
+    assert cnt.max() <= 255 and np.array_equal(cnt, np.round(cnt))
+    out["ug_cnt"] = cnt.astype(np.uint8)
+    out["mm_adj_row"], out["mm_adj_col"], out["mm_adj_val"] = mm_idx[0].astype(np.int16), mm_idx[1].astype(np.int16), mm_val
+    for n, v in init.items():
+        if n not in ("image_embedding.weight", "text_embedding.weight"):  # the feature tables, stored whole below
+            out["init." + n] = R.rows(_flat2(v), S["param"]).copy()
+    assert np.array_equal(init["image_embedding.weight"], model.v_feat.numpy())
+    assert np.array_equal(init["text_embedding.weight"], model.t_feat.numpy())
+    out["const.result_embed"] = result0.astype(np.float32)[::S["const"]].copy()
+    out["v_feat"], out["t_feat"] = model.v_feat.numpy().copy(), model.t_feat.numpy().copy()
+    rec = _Recorder(train)
+    _eval_dump(trainer, model, valid, "init_valid", out)
+    trained = R.trained()
+    P64 = R.cast({n: torch.from_numpy(v) for n, v in init.items() if n in trained}, torch.float64)
+    adam64 = R.Adam(P64, float(trainer.optimizer.param_groups[0]["lr"]))
+    losses = []
+    for epoch in range(2):
+        model.pre_epoch_processing()
+        idx_e = np.asarray(model.epoch_user_graph, dtype=np.int64)
+        W_e = model.user_weight_matrix.numpy().copy()
+        out[f"epoch{epoch}_idx"] = idx_e.astype(np.int16)
+        out[f"epoch{epoch}_W"] = W_e
+        if epoch == 0:
+            assert np.array_equal(idx_e, idx0) and np.array_equal(W_e, W0)
+        n0 = len(rec.batches)
+        adam64.lr = float(trainer.optimizer.param_groups[0]["lr"])
+        loss_sum, _ = trainer._train_epoch(train, epoch)
+        trainer.lr_scheduler.step()
+        losses.append(float(loss_sum))
+        out[f"epoch{epoch}_nbatch"] = np.int64(len(rec.batches) - n0)
+        for b in rec.batches[n0:]:
+            g64 = R.step(P64, f64, A64, mm64, layers, idx_e, torch.from_numpy(W_e).double(), b[:3].long(), nu,
+                         float(model.reg_weight))[4]
+            adam64.step(g64)
+        for name, prm in params:
+            if name in R.UNUSED:
+                assert np.array_equal(prm.detach().numpy(), init[name]), name
+                continue
+            out[f"epoch{epoch}_param." + name] = R.rows(_flat2(prm.detach().numpy()),
+                                                         S["last" if epoch == 1 else "epoch"]).copy()
+            dist = float((prm.detach().double() - P64[name].detach()).abs().max())
+            out[f"epoch{epoch}_f32_dist." + name] = np.float64(dist)
+            print(f"  epoch {epoch} {name}: float32 reference vs float64 restatement {dist:.3e} "
+                  f"(scale {float(prm.detach().abs().max()):.3e})")
+    out["epoch_losses"] = np.array(losses)
+    _eval_dump(trainer, model, valid, "epoch1_valid", out)
+    _eval_dump(trainer, model, test, "epoch1_test", out)
+    for tag, ld in (("valid", valid), ("test", test)):
+        out[f"{tag}_eval_u"] = ld.get_eval_users().numpy().astype(np.int64)
+        out[f"{tag}_eval_len"] = np.asarray(ld.get_eval_len_list(), dtype=np.int64)
+        out[f"{tag}_eval_items"] = np.concatenate([np.asarray(x, dtype=np.int64) for x in ld.get_eval_items()])
+    out["row_strides"] = np.array([f"{k}={v}" for k, v in S.items()])
+    out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()])
+    path = os.path.join(out_dir, "dragon_small.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}: {os.path.getsize(path) / 1e6:.2f} MB, keys={len(out)}")
+    limit = os.path.getsize(os.path.join(out_dir, "dualgnn_step0_small.npz"))
+    for f in ("dragon_small.npz", "dragon_step0_small.npz"):
+        assert os.path.getsize(os.path.join(out_dir, f)) < limit, f
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn | dualgnn")
+    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn | dualgnn | dragon")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     _install_shims()
@@ -1733,6 +1962,9 @@ def main():
         return
     if args.only == "dualgnn":
         capture_dualgnn(args.out)
+        return
+    if args.only == "dragon":
+        capture_dragon(args.out)
         return
     if args.only == "mf":
         capture_mf(args.out)
