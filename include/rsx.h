@@ -1949,6 +1949,71 @@ int rsx_dragon_loss_fwd(const rsx_dragon_loss_args* a, float* out, void* ws, siz
 int rsx_dragon_loss_bwd(const rsx_dragon_loss_args* a, const float* go, float* g_result, float* g_pref_v,
                         float* g_pref_t, float* g_weight_u, void* ws, size_t ws_bytes, rsx_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* SELFCFED_LGN (selfcf.hip)                                                  */
+/* ------------------------------------------------------------------------ */
+/*
+ * The per-step dropped graph (reference src/common/encoders.py:80-96): over a fixed CSR structure
+ * of nnz slots with the reverse-slot permutation rev (rev[rev[e]] = e, col[rev[e]] = row(e)),
+ *   val[e] = keep(e) ? val0[e] * scale : 0,   valT[rev[e]] = val[e]
+ * one launch, vector stores only, every slot of both buffers written exactly once.  Two modes:
+ *   hashed  keep_mask NULL: rate = a 24-bit uniform word in [0, 1) hashed from *seed (a device
+ *           word the caller advances once per training forward), keep(e) a hash of (*seed, e)
+ *           compared against rate, scale = 1 / (1 - rate) in f32;
+ *   replay  keep_mask [ceil(nnz / 32)] (bit e & 31 of word e / 32 = slot e kept) and *scale, a
+ *           device f32 word.
+ * info [2] (device) receives {rate, scale} as used (replay: rate = 1 - 1 / scale).  A rev entry
+ * outside [0, nnz) writes nothing.  nnz < 2^31 (else RSX_ERR_UNSUPPORTED); a NULL buffer, aliased
+ * buffers or a mode without its seed / scale: RSX_ERR_ARG; nnz = 0 is RSX_OK.  No allocation or
+ * synchronisation.
+ */
+int rsx_selfcf_edge_drop(const float* val0, const int32_t* rev, int64_t nnz, const int64_t* seed,
+                         const uint32_t* keep_mask, const float* scale, float* val, float* valT, float* info,
+                         rsx_stream_t stream);
+/*
+ * The bootstrap loss (reference src/models/selfcfed_lgn.py:41-69, src/common/loss.py:54-62) on the
+ * propagated table E [n_users + n_items, d] and the pairs (users[b], items[b]), b < batch:
+ *   x_u = E[u], x_i = E[n_users + i], q = x P^T + pb, t = dropout(x) (no gradient),
+ *   out = {total, ui, iu, reg}: ui = -mean cos(q_u, t_i) / 2, iu = -mean cos(q_i, t_u) / 2,
+ *   reg = 1/2 sum_b (|x_u|^2 + |x_i|^2) (repeats counted), total = ui + iu + reg_weight reg.
+ * cos as F.cosine_similarity (each norm clamped at 1e-8: an all-dropped target gives 0).  The
+ * dropout is keyed on the BATCH POSITION: mask [2, batch, d / 32] packed keep bits (user stream,
+ * then item stream) or, with mask NULL and p_drop > 0, a hash of (*seed, stream, b, column); kept
+ * values are x * (float)(1 / (1 - p_drop)).  A pair with an index outside its table makes every
+ * output word NaN and contributes nothing to any gradient.  Deterministic, no float atomics.
+ * rsx_selfcf_loss_bwd, after rsx_selfcf_loss_fwd with the same arguments and workspace: gE [n_users
+ * + n_items, d] written in full (exactly zero off the batch's rows; a row's occurrences summed in
+ * a fixed order), gP [d, d], gpb [d]; go: the upstream gradient, a device word.
+ * rsx_selfcf_targets: out [2 batch, d] = the targets, user stream then item stream.
+ * d in {64, 128}, 1 <= batch <= 65536 (else RSX_ERR_UNSUPPORTED; rsx_selfcf_ws_bytes: 0); ws_bytes
+ * < rsx_selfcf_ws_bytes(batch, d): RSX_ERR_WORKSPACE; a NULL pointer, p_drop outside [0, 1), or
+ * p_drop > 0 with neither seed nor mask: RSX_ERR_ARG; all before any launch.
+ */
+typedef struct rsx_selfcf_args {
+    int64_t n_users, n_items, batch;
+    int32_t d;
+    int32_t pad0;
+    const float *E, *P, *pb;
+    const int64_t *users, *items;
+    float reg_weight, p_drop;
+    const int64_t* seed;
+    const uint32_t* mask;
+    void* ws;
+    size_t ws_bytes;
+} rsx_selfcf_args;
+size_t rsx_selfcf_ws_bytes(int64_t batch, int32_t d);
+int rsx_selfcf_loss_fwd(const rsx_selfcf_args* a, float* out, rsx_stream_t stream);
+int rsx_selfcf_targets(const rsx_selfcf_args* a, float* out, rsx_stream_t stream);
+int rsx_selfcf_loss_bwd(const rsx_selfcf_args* a, const float* go, float* gE, float* gP, float* gpb,
+                        rsx_stream_t stream);
+/*
+ * The evaluation tables of the two-term score q_u . i + u . q_i (selfcfed_lgn.py:71-78) as one
+ * dot product at width 2 d: UC [n_users, 2 d] = [q_u | u], IC [n_items, 2 d] = [i | q_i], q the
+ * predictor on E's rows (rsx_linear_rows_fwd writes its half in place).  d in {64, 128}.
+ */
+int rsx_selfcf_eval_tables(const float* E, const float* P, const float* pb, int64_t n_users, int64_t n_items,
+                           int32_t d, float* UC, float* IC, rsx_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -174,6 +174,12 @@ class DragonLossArgs(C.Structure):
                 ("n_items", I64), ("batch", I64), ("d", I32), ("reg_weight", F32)]
 
 
+class SelfcfArgs(C.Structure):
+    _fields_ = [("n_users", I64), ("n_items", I64), ("batch", I64), ("d", I32), ("pad0", I32), ("E", P), ("P", P),
+                ("pb", P), ("users", P), ("items", P), ("reg_weight", F32), ("p_drop", F32), ("seed", P), ("mask", P),
+                ("ws", P), ("ws_bytes", C.c_size_t)]
+
+
 class LatticeGraph(C.Structure):
     _fields_ = [("n", I64), ("k", I32), ("n_mod", I32), ("f", I32), ("lam", F32), ("F", P * 2), ("idx", P * 2),
                 ("oidx", P * 2), ("oval", P * 2), ("modal_weight", P), ("w", P), ("invn", P * 2), ("a", P * 2),
@@ -353,6 +359,12 @@ def _declare(lib):
         "rsx_dragon_loss_ws_bytes": (C.c_size_t, [I64, I32]),
         "rsx_dragon_loss_fwd": (C.c_int, [C.POINTER(DragonLossArgs), P, P, C.c_size_t, P]),
         "rsx_dragon_loss_bwd": (C.c_int, [C.POINTER(DragonLossArgs), P, P, P, P, P, P, C.c_size_t, P]),
+        "rsx_selfcf_edge_drop": (C.c_int, [P, P, I64, P, P, P, P, P, P, P]),
+        "rsx_selfcf_ws_bytes": (C.c_size_t, [I64, I32]),
+        "rsx_selfcf_loss_fwd": (C.c_int, [C.POINTER(SelfcfArgs), P, P]),
+        "rsx_selfcf_targets": (C.c_int, [C.POINTER(SelfcfArgs), P, P]),
+        "rsx_selfcf_loss_bwd": (C.c_int, [C.POINTER(SelfcfArgs), P, P, P, P, P]),
+        "rsx_selfcf_eval_tables": (C.c_int, [P, P, P, I64, I64, I32, P, P, P]),
         "rsx_cpu_spmm": (C.c_int, [P, P, P, I64, P, I32, P]),
         "rsx_cpu_propagate_mean": (C.c_int, [P, P, P, I64, P, I32, I32, P]),
         "rsx_cpu_layergcn_forward": (C.c_int, [P, P, P, I64, P, I32, I32, P, P, P]),
@@ -407,6 +419,8 @@ EXPORTED = ["rsx_version", "rsx_csr_schedule_host", "rsx_csr_schedule_rebind", "
             "rsx_dualgnn_loss_fwd", "rsx_dualgnn_loss_bwd",
             "rsx_dragon_cat_fwd", "rsx_dragon_cat_bwd", "rsx_dragon_ugraph_fwd", "rsx_dragon_loss_ws_bytes",
             "rsx_dragon_loss_fwd", "rsx_dragon_loss_bwd",
+            "rsx_selfcf_edge_drop", "rsx_selfcf_ws_bytes", "rsx_selfcf_loss_fwd", "rsx_selfcf_targets",
+            "rsx_selfcf_loss_bwd", "rsx_selfcf_eval_tables",
             "rsx_cpu_spmm", "rsx_cpu_propagate_mean", "rsx_cpu_layergcn_forward", "rsx_cpu_layergcn_backward",
             "rsx_cpu_bpr", "rsx_cpu_fullsort_topk", "rsx_cpu_adam", "rsx_cpu_gcn_step_ws_floats", "rsx_cpu_gcn_step"]
 

@@ -88,13 +88,18 @@ def _join_tables(user_embedding: nn.Embedding, item_embedding: nn.Embedding, dev
     """Moves the two tables (created and initialised by the caller, on the CPU generator as the
     reference does) into adjacent row blocks of one device buffer: the UI backbone's ego table
     [U; I] is then that buffer itself (_ego), no per-forward concatenation copy."""
-    u, i = user_embedding.weight.detach(), item_embedding.weight.detach()
+    user_embedding.weight, item_embedding.weight = _join_params(user_embedding.weight, item_embedding.weight, device)
+
+
+def _join_params(u: torch.Tensor, i: torch.Tensor, device):
+    """_join_tables for two bare tables (a model that keeps nn.Parameters, not nn.Embeddings):
+    the two new nn.Parameters, adjacent row blocks of one device buffer."""
+    u, i = u.detach(), i.detach()
     nu = u.shape[0]
     joint = torch.empty(nu + i.shape[0], u.shape[1], dtype=torch.float32, device=device)
     joint[:nu].copy_(u)
     joint[nu:].copy_(i)
-    user_embedding.weight = nn.Parameter(joint[:nu])
-    item_embedding.weight = nn.Parameter(joint[nu:])
+    return nn.Parameter(joint[:nu]), nn.Parameter(joint[nu:])
 
 
 class _RowsOff(dict):

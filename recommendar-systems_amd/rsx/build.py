@@ -22,7 +22,7 @@ LIB = os.path.join(LIBDIR, "librsx.so")
 SOURCES = ["spmm.hip", "bpr.hip", "fullsort.hip", "step.hip", "smore.hip", "metrics.hip", "linear.hip", "dist.hip",
            "dp.hip", "smore_fuse.hip", "knn.hip", "graph.hip", "rowx.hip", "mf.hip", "bm3.hip", "mgcn.hip",
            "freedom.hip", "lattice.hip", "lgmrec.hip", "dense.hip", "mmgcn.hip", "grcn.hip", "dualgnn.hip",
-           "dragon.hip", "cpu_ops.cpp"]  # host-only C++ (the torch.ops.rsx CPU kernels), compiled as plain C++
+           "dragon.hip", "selfcf.hip", "cpu_ops.cpp"]  # host-only C++ (the torch.ops.rsx CPU kernels), compiled as plain C++
 ARCH = os.environ.get("RSX_OFFLOAD_ARCH", "gfx950")
 
 

@@ -14,7 +14,7 @@ MODELS = {"lightgcn": ("rsx.lightgcn", "LightGCN"), "layergcn": ("rsx.layergcn",
           "freedom": ("rsx.freedom", "FREEDOM"), "lattice": ("rsx.lattice", "LATTICE"),
           "lgmrec": ("rsx.lgmrec", "LGMRec"), "mmgcn": ("rsx.mmgcn", "MMGCN"),
           "grcn": ("rsx.grcn", "GRCN"), "dualgnn": ("rsx.dualgnn", "DualGNN"),
-          "dragon": ("rsx.dragon", "DRAGON")}
+          "dragon": ("rsx.dragon", "DRAGON"), "selfcfed_lgn": ("rsx.selfcf", "SELFCFED_LGN")}
 
 
 def get_local_time():

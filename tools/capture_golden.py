@@ -21,7 +21,7 @@ and move `result_embed` out of the CPU model's parameters (`_dualgnn_user_graph`
 Outputs are small `.npz` files under `tests/golden/` (data only: inputs and the
 reference's outputs). The reference itself never travels to the GPU box.
 
-Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn | dualgnn | dragon]
+Usage:  python tools/capture_golden.py [--out tests/golden] [--only small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn | dualgnn | dragon | selfcf]
 """
 from __future__ import annotations
 
@@ -1934,10 +1934,190 @@ def capture_dragon(out_dir):
         assert os.path.getsize(os.path.join(out_dir, f)) < limit, f
 
 
+def _selfcf_adj(model, out):
+    A = model.online_encoder.sparse_norm_adj
+    out["adj_idx"] = A._indices().numpy().astype(np.int32)  # the reference's own nonzero order
+    out["adj_val"] = A._values().numpy().astype(np.float32)
+
+
+class _SelfcfDraws:
+    """Records every sparse_dropout call of a reference LightGCN_Encoder: the rate numpy drew, the
+    f32 scale of the product, the keep mask torch.rand gave (in the encoder's nonzero order) and the
+    resulting values (zeros where dropped)."""
+
+    def __init__(self, enc):
+        self.rates, self.scales, self.keeps, self.vals = [], [], [], []
+        orig, rand = enc.sparse_dropout, torch.rand
+
+        def recording(x, rate, noise_shape):
+            drawn = []
+
+            def rand_rec(*a, **k):
+                drawn.append(rand(*a, **k))
+                return drawn[-1]
+
+            torch.rand = rand_rec
+            try:
+                y = orig(x, rate, noise_shape)
+            finally:
+                torch.rand = rand
+            assert len(drawn) == 1
+            keep = torch.floor((1 - rate) + drawn[0]).type(torch.bool)
+            scale = np.float32(1. / (1 - rate))
+            val = np.where(keep.numpy(), x._values().numpy() * scale, np.float32(0)).astype(np.float32)
+            yc = y.coalesce() if not y.is_coalesced() else y
+            assert yc._nnz() == int(keep.sum()) and np.array_equal(yc._values().numpy(), val[keep.numpy()])
+            self.rates.append(float(rate))
+            self.scales.append(scale)
+            self.keeps.append(keep.numpy().copy())
+            self.vals.append(val)
+            return y
+
+        enc.sparse_dropout = recording
+
+
+def _pack_bits(keep) -> np.ndarray:
+    keep = np.asarray(keep, dtype=bool).ravel()
+    pad = np.zeros((keep.size + 31) // 32 * 32, dtype=np.uint64)
+    pad[: keep.size] = keep
+    return (pad.reshape(-1, 32) << np.arange(32, dtype=np.uint64)).sum(-1).astype(np.uint32)
+
+
+def capture_selfcf(out_dir):
+    """SELFCFED_LGN (reference src/models/selfcfed_lgn.py on src/common/encoders.py) on the small
+    graph of the other fixtures, no feature files, seed 999, embedding_size 64, batches of 512.
+    selfcfed_lgn_step0_small.npz: n_layers 2, dropout 0.3, reg_weight 0.1: the initial parameters, the
+    graph, the first batch, the edge draw (rate, f32 scale, keep mask, resulting values), the two
+    [B, d] keep masks F.dropout drew, the loss, its terms and every gradient.
+    selfcfed_lgn_small.npz: n_layers 1, dropout 0.0: two epochs through the reference's Trainer with
+    every step's edge draw, laid out as bm3_small.npz.
+    Both also hold `refdiff.*`: per tensor the largest |reference - tests/selfcf_ref.py|, the float64
+    restatement run on the same draws."""
+    import torch.nn.functional as F
+
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import selfcf_ref as R
+
+    df = synth.amazon_like(400, 200, 4000, seed=7)
+    synth.write_inter(df, DATA_ROOT, "baby")
+    common = dict(train_batch_size=512, eval_batch_size=256, is_multimodal_model=False)
+
+    from utils.utils import init_seed, get_model
+
+    over = dict(common, n_layers=[2], dropout=[0.3], reg_weight=[0.1])
+    config, train, _, _ = _load("SELFCFED_LGN", "baby", over)
+    hp = _select_hparams(config)
+    init_seed(config["seed"])
+    train.pretrain_setup()
+    model = get_model("SELFCFED_LGN")(config, train)
+    out = {"n_users": np.int64(model.n_users), "n_items": np.int64(model.n_items)}
+    inter = train.inter_matrix(form="coo")
+    out["train_u"], out["train_i"] = inter.row.astype(np.int64), inter.col.astype(np.int64)
+    _selfcf_adj(model, out)
+    out["param_names"] = np.array([n for n, _ in model.named_parameters()])
+    for n, p in _param_dict(model).items():
+        out["init." + n] = p.numpy()
+    batch = next(iter(train))
+    draws = _SelfcfDraws(model.online_encoder)
+    keeps = []
+    orig = F.dropout
+
+    def recording(x, p=0.5, training=True, inplace=False):
+        y = orig(x, p, training, inplace)
+        keeps.append((y != 0) | (x == 0))  # a zero input: kept or not makes no difference
+        return y
+
+    F.dropout = recording
+    try:
+        model.train()
+        loss = model.calculate_loss(batch)
+    finally:
+        F.dropout = orig
+    loss.backward()
+    assert len(keeps) == 2 and len(draws.rates) == 1
+    out["pairs"] = batch.numpy().astype(np.int16)
+    out["rate"], out["scale"] = np.float64(draws.rates[0]), np.float32(draws.scales[0])
+    out["edge_keep"] = _pack_bits(draws.keeps[0])
+    out["drop_val"] = draws.vals[0]
+    out["keep_user"], out["keep_item"] = _pack_keep(keeps[0].numpy()), _pack_keep(keeps[1].numpy())
+    out["step0_loss"] = np.float64(loss.item())
+    for n, p in model.named_parameters():
+        out["step0_grad." + n] = p.grad.numpy().copy()
+    n = int(model.n_users + model.n_items)
+    keep = np.stack([keeps[0].numpy(), keeps[1].numpy()])
+    params = {k: out["init." + k] for k in R.NAMES}
+    A = R.dense_adj(out["adj_idx"], out["drop_val"].astype(np.float64), n)
+    us, it = batch[0].numpy(), batch[1].numpy()
+    rout, rg = R.model_loss_grad(params, A, 2, us, it, 0.1, 0.3, keep, scale=float(np.float32(1 / (1 - 0.3))))
+    # the three terms by the reference's own modules on the recorded draws (their weighted sum is the loss)
+    with torch.no_grad():
+        enc = model.online_encoder
+        ego = torch.cat([enc.embedding_dict["user_emb"], enc.embedding_dict["item_emb"]], 0)
+        Ad = torch.sparse_coo_tensor(torch.from_numpy(out["adj_idx"].astype(np.int64)),
+                                     torch.from_numpy(out["drop_val"]), (n, n))
+        embs = [ego]
+        for _ in range(2):
+            embs.append(torch.sparse.mm(Ad, embs[-1]))
+        E = torch.stack(embs, dim=1).mean(dim=1)
+        xu, xi = E[: model.n_users][batch[0]], E[model.n_users:][batch[1]]
+        tu, ti = xu * keeps[0] / (1 - 0.3), xi * keeps[1] / (1 - 0.3)
+        terms = [float(model.loss_fn(model.predictor(xu), ti) / 2), float(model.loss_fn(model.predictor(xi), tu) / 2),
+                 float(model.reg_loss(xu, xi))]
+    total = terms[0] + terms[1] + 0.1 * terms[2]
+    assert abs(total - loss.item()) <= 1e-5 * abs(loss.item()), (total, loss.item())
+    out["step0_terms"] = np.array(terms, dtype=np.float64)
+    out["refdiff.loss"] = np.float64(abs(rout[0] - loss.item()))
+    for k in R.NAMES:
+        out["refdiff.grad." + k] = np.float64(np.abs(rg[k] - out["step0_grad." + k]).max())
+    out["hparams"] = np.array([f"{k}={v}" for k, v in hp.items()])
+    path = os.path.join(out_dir, "selfcfed_lgn_step0_small.npz")
+    np.savez_compressed(path, **out)
+    print(f"wrote {path}: {os.path.getsize(path) / 1e6:.2f} MB, keys={len(out)}")
+    print("  refdiff:", {k: float(v) for k, v in out.items() if k.startswith("refdiff.")})
+
+    # ---- two epochs through the reference's Trainer, every step's edge draw recorded
+    tap = {}
+
+    def extra(model, o, tag):
+        if tag == "pre":
+            _selfcf_adj(model, o)
+        elif tag == "e0":
+            tap["draws"] = _SelfcfDraws(model.online_encoder)
+
+    def post(arrays):
+        d = tap["draws"]
+        keep = {}
+        for k, v in _mf_stored(arrays).items():
+            if k.startswith("step0_"):
+                continue
+            if k.endswith("_triplets"):
+                keep[k[: -len("_triplets")] + "_pairs"] = v.astype(np.int16)
+            else:
+                keep[k] = v
+        keep["step_rate"] = np.array(d.rates, dtype=np.float64)
+        keep["step_scale"] = np.array(d.scales, dtype=np.float32)
+        keep["step_edge_keep"] = np.stack([_pack_bits(k) for k in d.keeps])
+        nb = [int(arrays[f"epoch{e}_nbatch"]) for e in range(2)]
+        assert len(d.rates) == sum(nb)
+        pairs = [q for e in range(2) for q in R.epoch_pairs(keep, e)]
+        steps = [(q, k, s) for q, k, s in zip(pairs, d.keeps, d.scales)]
+        p1, losses = R.train({k: arrays["init." + k] for k in R.NAMES}, arrays["adj_idx"], arrays["adj_val"], 1,
+                             steps, 0.1, 0.0)
+        for k in R.NAMES:
+            keep["refdiff.param." + k] = np.float64(np.abs(p1[k] - arrays["epoch1_param." + k]).max())
+        ep = np.array([losses[: nb[0]].sum(), losses[nb[0]:].sum()])
+        keep["refdiff.epoch_losses"] = np.float64(np.abs(ep - arrays["epoch_losses"]).max())
+        print("  refdiff:", {k: float(v) for k, v in keep.items() if k.startswith("refdiff.")})
+        return keep
+
+    capture_model_full("SELFCFED_LGN", "baby", dict(common, n_layers=[1], dropout=[0.0], reg_weight=[0.1]),
+                       os.path.join(out_dir, "selfcfed_lgn_small.npz"), epochs=2, extra=extra, post=post)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(REPO, "tests", "golden"))
-    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn | dualgnn | dragon")
+    ap.add_argument("--only", default=None, help="capture one fixture set: small | smore_d128 | mf | bm3 | mgcn | freedom | lattice | lgmrec | grcn | mmgcn | dualgnn | dragon | selfcf")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
     _install_shims()
@@ -1971,6 +2151,9 @@ def main():
         return
     if args.only == "bm3":
         capture_bm3(args.out)
+        return
+    if args.only == "selfcf":
+        capture_selfcf(args.out)
         return
     if args.only in (None, "smore_d128"):
         capture_smore_d128(args.out)
